@@ -24,12 +24,20 @@ time over ranks. ``vs_baseline`` compares like with like: tokens/s *per GPU*
 against the reference's 6,376 tokens/s on its one GPU (the BASELINE metric is
 "tokens/sec/GPU"), so it does not grow with N by itself.
 
-After the timed steps (outside the timed region) the second half of the
-BASELINE metric is measured on the same state: the checkpoint save wall-clock
-(exit path, blocking until durable) and the training-visible cost of a
-periodic save that overlaps the next steps (``ckpt_save``; ``--no-ckpt`` skips
-it). Under data parallelism the collective exposure is estimated by re-running
-the same steps with every collective skipped (``exposed_comm_ms_per_step``).
+A plain run sets up, warms up, times the steps and prints the line. ``--full``
+adds the measurements that take runs of their own, after the timed steps
+(outside the timed region) and on the same state: the second half of the
+BASELINE metric, i.e. the checkpoint save wall-clock (exit path, blocking until
+durable) and the training-visible cost of a periodic save that overlaps the
+next steps (``ckpt_save``; ``--no-ckpt`` skips it), and under data parallelism
+the collective exposure, estimated by re-running the same steps with every
+collective skipped (``exposed_comm_ms_per_step``; ``--no-exposed-comm`` skips it).
+
+``--dump-outputs DIR`` writes what the last timed step computed as
+``DIR/<name>.npy`` (float32): the loss, the gradient norm, and a fixed seeded
+sample of the updated parameters and AdamW moments (see ``dump_outputs``). Model
+init and the synthetic batches are seeded, so two builds run with the same
+arguments are compared output for output.
 """
 from __future__ import annotations
 
@@ -58,12 +66,19 @@ def parse():
                     help="gradient / optimizer bucket MiB (default: 64 on one GPU, 256 under DP)")
     ap.add_argument("--ckpt-dir", default="", help="directory for the checkpoint-save measurement "
                     "(default: $FT_BENCH_CKPT_DIR or <tmpdir>/ft_bench_ckpt)")
-    ap.add_argument("--no-ckpt", action="store_true", help="skip the checkpoint-save measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checkpoint-save measurement and (N > 1) the "
+                         "exposed-collective estimate; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (loss, grad norm, sampled parameters and "
+                         "AdamW moments) as DIR/<name>.npy")
+    ap.add_argument("--no-ckpt", action="store_true", help="with --full: skip the checkpoint-save measurement")
     ap.add_argument("--ckpt-mode", default="auto", choices=["auto", "hbm", "host"],
                     help="checkpoint snapshot: 'hbm' (D2D into spare HBM, then drained to host), 'host' "
                          "(straight to pinned host memory), 'auto' (hbm when the free HBM holds it)")
     ap.add_argument("--grad-accum", type=int, default=1, help="micro-batches per optimizer step")
-    ap.add_argument("--no-exposed-comm", action="store_true", help="skip the DP exposed-collective estimate")
+    ap.add_argument("--no-exposed-comm", action="store_true",
+                    help="with --full: skip the DP exposed-collective estimate")
     ap.add_argument("--graph", action="store_true",
                     help="replay each step as one HIP graph (optimizer of step k with forward/backward of "
                          "step k+1, the RCCL bucket collectives captured under DP): launch-bound presets")
@@ -84,6 +99,37 @@ def parse():
 def _sync(dev):
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
+
+
+DUMP_SAMPLE = 1 << 22  # elements kept of each large buffer: 16 MiB as float32, 48 MiB for the three
+
+
+def _sample(t, seed):
+    """``t`` itself when it is small, else DUMP_SAMPLE of its elements at fixed (seeded, sorted)
+    positions that depend only on its length."""
+    if t.numel() <= DUMP_SAMPLE:
+        return t
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+    return t.index_select(0, idx.to(t.device))
+
+
+def dump_outputs(d, loss, grad_norm, model, opt):
+    """What a caller of the timed step receives from its last step, as float32 ``.npy`` files: the
+    loss it returns, the pre-clip gradient norm, and the state it leaves behind (the flat parameter
+    buffer and the AdamW moments, this rank's shard of them under ZeRO-1)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    arrays = {
+        "loss": torch.as_tensor(loss).reshape(1),
+        "grad_norm": torch.as_tensor(float("nan") if grad_norm is None else grad_norm).reshape(1),
+        "params": _sample(model.flat.params.detach(), 1),
+        "exp_avg": _sample(opt.exp_avg.detach(), 2),
+        "exp_avg_sq": _sample(opt.exp_avg_sq.detach(), 3),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.float().cpu().numpy())
 
 
 def _launched_world():
@@ -245,7 +291,9 @@ def main():
     elapsed = fdist.ctrl_allreduce_max(int(elapsed * 1e9)) / 1e9
     # each rank's loss is its token sum over the GLOBAL token count: the global mean is the sum
     final_loss = fdist.ctrl_allreduce_sum(float(loss.item())) if world > 1 else float(loss.item())
-    opt.check_finite(block=True)
+    grad_norm = opt.check_finite(block=True)
+    if a.dump_outputs and info.is_main:
+        dump_outputs(a.dump_outputs, final_loss, grad_norm, model, opt)
 
     ms = elapsed / a.steps * 1e3
     tok_s = B * K * S * world * a.steps / elapsed
@@ -309,7 +357,7 @@ def main():
     if K > 1:
         out["grad_accum"] = K
     nxt = a.warmup + a.steps
-    if world > 1 and not a.no_exposed_comm:
+    if a.full and world > 1 and not a.no_exposed_comm:
         # same steps with every collective skipped: the difference is what the ranks wait for
         n = max(3, min(10, a.steps))
         red.dry_comm = True
@@ -326,7 +374,7 @@ def main():
         dry = fdist.ctrl_allreduce_max(int(dry * 1e6)) / 1e6
         out["compute_only_ms_per_step"] = round(dry, 2)
         out["exposed_comm_ms_per_step"] = round(ms - dry, 2)
-    if not a.no_ckpt:
+    if a.full and not a.no_ckpt:
         import tempfile
 
         from fault_tolerant_llm_training_amd.ckpt.bench_save import measure_checkpoint

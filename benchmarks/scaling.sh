@@ -13,7 +13,7 @@ for N in 1 2 4 8; do
     python bench.py --gpus 1 --steps $STEPS --warmup $WARM --no-ckpt "$@" | tee -a "$OUT"
   else
     python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-      --master-port $((29600 + N)) bench.py --gpus $N --steps $STEPS --warmup $WARM --no-ckpt "$@" | tee -a "$OUT"
+      --master-port $((29600 + N)) bench.py --gpus $N --steps $STEPS --warmup $WARM --full --no-ckpt "$@" | tee -a "$OUT"
   fi
 done
 python - "$OUT" <<'PY'

@@ -52,8 +52,8 @@ def _check_ckpt(j, world):
 
 
 def test_bench_single_process_json(tmp_path):
-    r = subprocess.run([sys.executable, "bench.py"] + ARGS, cwd=ROOT, env=_env(tmp_path), capture_output=True,
-                       text=True, timeout=300)
+    r = subprocess.run([sys.executable, "bench.py", "--full"] + ARGS, cwd=ROOT, env=_env(tmp_path),
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
@@ -66,10 +66,61 @@ def test_bench_single_process_json(tmp_path):
     _check_ckpt(j, 1)
 
 
+def test_bench_plain_run_times_only_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the run stops after the timed steps (no checkpoint block); ``--steps`` sets
+    the number of timed steps; ``--dump-outputs`` writes the last step's results as float32 ``.npy``
+    files that are identical from run to run (seeded model and batches)."""
+    import numpy as np
+
+    dumps = []
+    for name, steps in (("a", 3), ("b", 3), ("c", 4)):
+        d = tmp_path / name
+        args = ARGS + ["--steps", str(steps)]
+        r = subprocess.run([sys.executable, "bench.py", "--dump-outputs", str(d)] + args, cwd=ROOT,
+                           env=_env(tmp_path / "ck"), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1
+        j = lines[0]
+        assert j["steps"] == steps and j["ms_per_step"] > 0
+        assert "ckpt_save" not in j and not (tmp_path / "ck").exists()
+        arrs = {p.stem: np.load(p) for p in sorted(d.glob("*.npy"))}
+        assert set(arrs) == {"loss", "grad_norm", "params", "exp_avg", "exp_avg_sq"}
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in arrs.values())
+        assert sum(v.nbytes for v in arrs.values()) <= 64 * 2**20
+        # the tiny model is below the sample size: the whole (aligned) flat buffers
+        assert arrs["params"].size >= j["params"] and arrs["exp_avg"].shape == arrs["params"].shape
+        assert abs(float(arrs["loss"][0]) - j["final_loss"]) < 1e-3
+        dumps.append(arrs)
+    a, b, c = dumps
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    # one more timed step is one more optimizer step: the dump follows --steps
+    assert not np.array_equal(a["params"], c["params"])
+
+
+def test_bench_dump_sample_is_fixed():
+    """Buffers above the sample size are dumped at fixed sorted positions that depend only on the
+    buffer's length; smaller ones whole."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    try:
+        import bench
+    finally:
+        sys.path.remove(ROOT)
+    t = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    s1, s2 = bench._sample(t, 1), bench._sample(t.clone(), 1)
+    assert s1.numel() == bench.DUMP_SAMPLE and torch.equal(s1, s2)
+    assert bool((s1[1:] >= s1[:-1]).all()) and not torch.equal(s1, bench._sample(t, 2))
+    small = torch.arange(10.0)
+    assert bench._sample(small, 1) is small
+
+
 @pytest.mark.parametrize("mode", ["zero1", "allreduce"])
 def test_bench_torchrun_two_ranks(mode, tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--dp-mode", mode] + ARGS
+           "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", "2", "--full", "--dp-mode", mode] + ARGS
     r = subprocess.run(cmd, cwd=ROOT, env=_env(tmp_path), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -100,7 +151,7 @@ def test_bench_torchrun_n_ranks_zero1(world, tmp_path):
     default ZeRO-1 mode with 64-element-aligned shards, the sparse embedding exchange across all
     ranks, the exposed-communication re-timing and the sharded checkpoint block."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
-           "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(world)] + ARGS
+           "--master-addr", "127.0.0.1", "--master-port", str(_port()), "bench.py", "--gpus", str(world), "--full"] + ARGS
     r = subprocess.run(cmd, cwd=ROOT, env=_env(tmp_path), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
