@@ -247,10 +247,18 @@ __device__ __forceinline__ void map_head(int hh, int Hq, int Hkv, int& h, int& k
 // softmax and K/V buffers, and merge (m, l, O) through LDS at the end. That halves the causal
 // critical path (the last query tile's sweep over all keys) and gives every SIMD two waves, so
 // one's softmax overlaps the other's MFMAs.
-template <class E, int D, int NW = 4, int SPLIT = 1>
+// DOC (flash_doc_fwd; unsplit only): document-masked attention for packed sequences. doc_start
+// [B, S] int32 (non-decreasing per sequence, doc_start[i] <= i) gives each query's first visible
+// key: the block's key loop starts at the tile of its first row's doc_start, a wave skips tiles
+// wholly in front of its first row's document, and tiles that hold a boundary of one of the wave's
+// rows take the masked path with key < doc_start[qrow] added to the causal mask. The values only
+// bound loops and feed compares; no address is formed from them.
+template <class E, int D, int NW = 4, int SPLIT = 1, bool DOC = false>
 __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_kernel(
     const bf16_t* __restrict__ qk, const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
-    float* __restrict__ lse2, int B, int S, int Hq, int Hkv, float sl2, long ldqk_) {
+    float* __restrict__ lse2, int B, int S, int Hq, int Hkv, float sl2, long ldqk_,
+    const int* __restrict__ doc_start = nullptr) {
+  static_assert(!DOC || SPLIT == 1, "the document mask is built into the unsplit kernel only");
   constexpr int BM = 32 * NW, BN = 64, KS = D / 16, NDB = D / 32;
   constexpr int TILE = BN * D * 2;
   // K | V tiles by LDS-DMA into two separate LDS objects, loop unrolled by two (as in the
@@ -294,6 +302,16 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
 
   const int kend = min((qt + 1) * BM, S);
   const int ntiles = (kend + BN - 1) / BN;
+  // DOC: first key tile of the block (clamped to [0, ntiles]), this lane's first visible key, and
+  // the first visible keys of the wave's first / last rows (the smallest / largest of the wave)
+  int it0 = 0, dsq = 0, dsw0 = 0, dsw1 = 0;
+  if constexpr (DOC) {
+    const int* dsg = doc_start + (long)b * S;
+    it0 = max(0, min(dsg[min(qt * BM, S - 1)] / BN, ntiles));
+    dsq = dsg[min(qrow, S - 1)];
+    dsw0 = dsg[min(q0, S - 1)];
+    dsw1 = dsg[min(q0 + 31, S - 1)];
+  }
   constexpr int GPW = TILE / 1024 / NW;  // glds instructions per wave per image
   auto dma = [&](int KT, auto BUF) {
     char* kb_ = (decltype(BUF)::value ? kv1 : kv0) + half * 2 * TILE;
@@ -306,7 +324,11 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
       glds16(Vg + key * ldv + c * 8, kb_ + TILE + piece * 1024);
     });
   };
-  if (half < ntiles) dma(half, std::integral_constant<int, 0>{});
+  if constexpr (DOC) {
+    if (it0 < ntiles) dma(it0, std::integral_constant<int, 0>{});
+  } else {
+    if (half < ntiles) dma(half, std::integral_constant<int, 0>{});
+  }
 
   f32x16_t o[NDB];
 #pragma unroll
@@ -329,7 +351,9 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
     const char* kb = (cur ? kv1 : kv0) + half * 2 * TILE;
     const char* vb = kb + TILE;
     const int k0 = kt * BN;
-    const bool v0 = k0 <= q0 + 31;       // wave-uniform: sub-tile 0 has an unmasked key
+    // wave-uniform: sub-tile 0 has an unmasked key (DOC: and the tile reaches the first document
+    // of the wave's rows)
+    const bool v0 = k0 <= q0 + 31 && (!DOC || k0 + BN > dsw0);
     const bool v1 = k0 + 32 <= q0 + 31;  // sub-tile 1
     // Two code paths: tiles strictly below the diagonal need no masking at all
     // (most of them), diagonal tiles mask per element. Wave-uniform branch.
@@ -356,6 +380,9 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
           if constexpr (MASK) {
             const int key = k0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
             if ((j == 1 && !v1) || key > qrow) x = -INFINITY;
+            if constexpr (DOC) {
+              if (key < dsq) x = -INFINITY;
+            }
             s[j][r] = x;
           }
           mx = fmaxf(mx, x);
@@ -369,7 +396,12 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
       const float cand = mx * sl2;
       if (__any(cand > m + RESCALE_LOG2)) {
         const float mn = fmaxf(m, cand);
-        const float alpha = fast_exp2(m - mn);
+        float alpha = fast_exp2(m - mn);
+        if constexpr (DOC) {
+          // a row whose document starts behind this tile is still empty while a wave-mate's
+          // max moves: m = mn = -inf, and exp2(-inf - -inf) is NaN; its l and O are 0: keep them
+          if (mn == -INFINITY) alpha = 1.f;
+        }
         m = mn;
         l *= alpha;
 #pragma unroll
@@ -382,7 +414,12 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float p = fast_exp2(fmaf(s[j][r], sl2, -m));
+          float p = fast_exp2(fmaf(s[j][r], sl2, -m));
+          if constexpr (DOC && MASK) {
+            // masked entries give 0 whatever m is (a still-empty row has m = -inf: the exponent
+            // above is -inf + inf)
+            if (s[j][r] == -INFINITY) p = 0.f;
+          }
           ls += p;
           s[j][r] = p;
         }
@@ -403,7 +440,8 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
       }
     };
     if (v0 && kt < ntiles) {
-      if (k0 + BN - 1 > q0)  // some key may exceed some query of this wave
+      // some key may exceed some query of this wave (DOC: or precede some row's document)
+      if (k0 + BN - 1 > q0 || (DOC && k0 < dsw1))
         tile(std::true_type{});
       else
         tile(std::false_type{});
@@ -412,7 +450,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, 8 / (NW * SPLIT)) void flash_fwd_k
     __syncthreads();                // ... and everyone's; nobody reads this tile any more
   };
   const int nit = (ntiles + SPLIT - 1) / SPLIT;
-  for (int it = 0; it < nit; it += 2) {
+  for (int it = it0; it < nit; it += 2) {  // (it0 = 0 without DOC)
     iter(it, std::integral_constant<int, 0>{});
     if (it + 1 < nit) iter(it + 1, std::integral_constant<int, 1>{});
   }
@@ -1133,12 +1171,22 @@ __device__ __forceinline__ void gqa_fold_rows(const bf16_t* __restrict__ dk_part
 // rows and every wave forms the slice's delta = rowsum(dO * O) itself (the dQ kernel's arithmetic,
 // term for term: bitwise the same values), so this kernel runs FIRST and the dQ kernel after it
 // folds the GQA partials (no finalize pass).
-template <class E, int D, int NW = 4, int SPLIT = 1, bool SD = false>
+// DOC (flash_doc_bwd; unsplit, no SD): document-masked attention. Key j is seen by the queries
+// j <= i < doc_end[j] (doc_end [B, S] int32, non-decreasing per sequence): the key tile's sweep
+// stops with the pair that holds row doc_end - 1 of the tile's last valid key, and slices that reach
+// doc_end of the wave's first key take the masked path with q >= doc_end[key] added -- for
+// consistent boundaries the same element mask as doc_start[q] > key. The per-key doc_end sits in
+// LDS (BK ints) and is read back by the masked slices only, in a pass of its own behind the slice's
+// statistics: neither 32 staged doc_start values per slice nor a register held across the sweep fit
+// the register budget (profiles/flash_doc.md). The values are clamped to [0, S] when loaded; they
+// only bound the sweep and feed compares.
+template <class E, int D, int NW = 4, int SPLIT = 1, bool SD = false, bool DOC = false>
 __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SPLIT)) void flash_bwd_dkdv2_kernel(
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ qk, const bf16_t* __restrict__ qkv,
     const float* __restrict__ lse2, const float* __restrict__ delta, bf16_t* __restrict__ dk_part,
     bf16_t* __restrict__ dv_part, long ldkv, int B, int S, int Hq, int Hkv, float sl2, float scale, long ldqk_,
-    GqaFold fold, const bf16_t* __restrict__ O = nullptr) {
+    GqaFold fold, const bf16_t* __restrict__ O = nullptr, const int* __restrict__ doc_end = nullptr) {
+  static_assert(!DOC || (SPLIT == 1 && !SD), "the document mask is built into the unsplit kernel only");
   constexpr int BK = 32 * NW, BQ = 32, KS = D / 16, NDB = D / 32;
   constexpr int QIMG = BQ * D * 2;          // one Q or dO slice
   constexpr int STO = (SD ? 3 : 2) * QIMG;  // lse[32] | delta[32] after Q | dO (| O)
@@ -1179,7 +1227,23 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
 
   const int qs0 = kb0 / BQ;
   const int n = (S + BQ - 1) / BQ - qs0;  // slices of this key tile (>= 1)
-  const int npairs = (n + 1) / 2;
+  int npairs = (n + 1) / 2;
+  // DOC: doc_end, clamped to [0, S], of the block's keys in LDS (read back by the masked slices
+  // only: a register held across the sweep does not fit the 2-wave kernel's 256) and of the wave's
+  // first key (the wave's smallest): queries from `lim` on are masked for some key of the wave, or
+  // lie beyond S.
+  __shared__ int sdek[DOC ? BK : 1];
+  int lim = S;
+  if constexpr (DOC) {
+    const int* deg = doc_end + (long)b * S;
+    // the sweep ends with the slice that holds row doc_end - 1 of the tile's last valid key
+    const int det = max(0, min(deg[min(kb0 + BK, S) - 1], S));
+    // (only the pair count shrinks: a last pair's second slice behind it is masked out whole;
+    // a shortened slice count of its own costs the 2-wave kernel a scalar it has no room for)
+    npairs = max(0, min(((det + BQ - 1) / BQ - qs0 + 1) / 2, npairs));
+    sdek[wave * 32 + l32] = max(0, min(deg[min(kw + l32, S - 1)], S));  // both lane halves: same value
+    lim = max(0, min(deg[min(kw, S - 1)], S));
+  }
   constexpr int GPW = QIMG / 1024 / NW;   // glds instructions per wave per image
   // pair p -> buffer: slices 2p (A) and 2p+1 (B, if any)
   auto dma = [&](int p, char* buf) __attribute__((always_inline)) {
@@ -1275,6 +1339,17 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
         sv[r] = p;
       }
     });
+    if constexpr (DOC && MASK) {
+      // the document mask in a pass of its own, behind the slice's statistics: the lane's doc_end
+      // is live only here
+      const int dek = sdek[wave * 32 + l32];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool off = qb + (r & 3) + 8 * (r >> 2) + 4 * hi >= dek;
+        sv[r] = off ? 0.f : sv[r];
+        dpv[r] = off ? 0.f : dpv[r];
+      }
+    }
     const typename FA<E>::v8 pa[2] = {cvt8<E, 0>(sv), cvt8<E, 8>(sv)};
     const typename FA<E>::v8 da[2] = {cvt8<E, 0>(dpv), cvt8<E, 8>(dpv)};
 #pragma unroll
@@ -1291,7 +1366,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     if (qb + BQ - 1 < kw) return;  // wave-uniform: all of the slice is above this wave's keys
     f32x16_t sv, dpv;
     sdp(sl, sv, dpv);
-    if (kw + 31 > qb || qb + BQ > S)
+    if (kw + 31 > qb || qb + BQ > (DOC ? lim : S))
       fin(sl, i, sv, dpv, std::true_type{});
     else
       fin(sl, i, sv, dpv, std::false_type{});
@@ -1314,7 +1389,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     // steady state: both slices entirely below this wave's diagonal and inside S
     if (p >= npairs) {
       // idle (this half-block has no pair left)
-    } else if (ib < n && qa >= kw + 31 && qa + 2 * BQ <= S) {
+    } else if (ib < n && qa >= kw + 31 && qa + 2 * BQ <= (DOC ? lim : S)) {
       f32x16_t sa, dpa, sb, dpb;
       // the compiler's default schedule keeps the pair's phases apart; the IGLP
       // "DS + MFMA interleave" strategy spreads the LDS reads and the VALU between the
@@ -1449,13 +1524,17 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
 // O != null: the kernel forms delta = rowsum(dO * O) itself (each lane pair already holds its
 // query's dO row) and publishes it for the dK/dV kernel that runs after it — the separate
 // flash_bwd_pre pass and its second read of dO are gone.
-template <class E, int D, int NW = 4, int SPLIT = 1>
+// DOC (flash_doc_bwd; unsplit only): the document mask of flash_fwd_kernel<.., DOC> — the same
+// loop start, per-wave tile skip, masked-path condition and key < doc_start[qrow] element mask.
+template <class E, int D, int NW = 4, int SPLIT = 1, bool DOC = false>
 __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SPLIT)) void flash_bwd_dq_kernel(
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ qk, const bf16_t* __restrict__ qkv,
     const float* __restrict__ lse2, float* __restrict__ delta, bf16_t* __restrict__ dqkv, int B,
     int S, int Hq, int Hkv, float sl2, float scale, long ldqk_, const bf16_t* __restrict__ O,
     const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-    const bf16_t* __restrict__ dk_part = nullptr, const bf16_t* __restrict__ dv_part = nullptr) {
+    const bf16_t* __restrict__ dk_part = nullptr, const bf16_t* __restrict__ dv_part = nullptr,
+    const int* __restrict__ doc_start = nullptr) {
+  static_assert(!DOC || SPLIT == 1, "the document mask is built into the unsplit kernel only");
   constexpr int BM = 32 * NW, BN = 64, KS = D / 16, NDB = D / 32;
   constexpr int TILE = BN * D * 2;
   // K | V tiles arrive by LDS-DMA (no staging VGPRs held across the compute: at one wave
@@ -1518,6 +1597,15 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
 
   const int kend = min((qt + 1) * BM, S);
   const int ntiles = (kend + BN - 1) / BN;
+  // DOC: as in flash_fwd_kernel (first tile clamped to [0, ntiles]; compares only)
+  int it0 = 0, dsq = 0, dsw0 = 0, dsw1 = 0;
+  if constexpr (DOC) {
+    const int* dsg = doc_start + (long)b * S;
+    it0 = max(0, min(dsg[min(qt * BM, S - 1)] / BN, ntiles));
+    dsq = dsg[qr];
+    dsw0 = dsg[min(q0, S - 1)];
+    dsw1 = dsg[min(q0 + 31, S - 1)];
+  }
   constexpr int GPW = TILE / 1024 / NW;  // glds instructions per wave per image
   // tile KT -> buffer BUF: each lane moves one 16-B chunk; the swizzle is on the source
   auto dma = [&](int KT, auto BUF) {
@@ -1532,7 +1620,11 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     });
   };
 
-  if (half < ntiles) dma(half, std::integral_constant<int, 0>{});
+  if constexpr (DOC) {
+    if (it0 < ntiles) dma(it0, std::integral_constant<int, 0>{});
+  } else {
+    if (half < ntiles) dma(half, std::integral_constant<int, 0>{});
+  }
   // Materialise the Q / dO fragments and row statistics before the loop: left pending,
   // the compiler's waits for them inside the loop would drain the next tile's prefetch.
   asm volatile("" ::"v"(lq), "v"(dlq));
@@ -1555,7 +1647,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     const char* kb = (cur ? kv1 : kv0) + half * 2 * TILE;
     const char* vb = kb + TILE;
     const int k0 = kt * BN;
-    const bool v0 = k0 <= q0 + 31;
+    const bool v0 = k0 <= q0 + 31 && (!DOC || k0 + BN > dsw0);
     const bool v1 = k0 + 32 <= q0 + 31;
     auto tile = [&](auto MASKED) {
       constexpr bool MASK = decltype(MASKED)::value;
@@ -1580,6 +1672,9 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
           if constexpr (MASK) {
             const int key = k0 + j * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
             if ((j == 1 && !v1) || key > qrow || qrow >= S) p = 0.f;
+            if constexpr (DOC) {
+              if (key < dsq) p = 0.f;
+            }
           }
           sc[j][r] = p * (dp[j][r] - dlq);
         }
@@ -1600,7 +1695,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     };
     if (v0 && kt < ntiles) {
       // rows >= S (ragged last tile) take the masked path too
-      if (k0 + BN - 1 > q0 || q0 + 31 >= S)
+      if (k0 + BN - 1 > q0 || q0 + 31 >= S || (DOC && k0 < dsw1))
         tile(std::true_type{});
       else
         tile(std::false_type{});
@@ -1609,7 +1704,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     __syncthreads();                // ... and everyone's; nobody reads tile kt any more
   };
   const int nit = (ntiles + SPLIT - 1) / SPLIT;
-  for (int it = 0; it < nit; it += 2) {
+  for (int it = it0; it < nit; it += 2) {  // (it0 = 0 without DOC)
     iter(it, std::integral_constant<int, 0>{});
     if (it + 1 < nit) iter(it + 1, std::integral_constant<int, 1>{});
   }
@@ -2052,6 +2147,139 @@ at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Ten
   return dqkv;
 }
 
+// ================================================================== document-masked attention
+// Packed sequences (several documents per sequence): query i sees the keys doc_start[i] <= j <= i,
+// i.e. key j is seen by the queries j <= i < doc_end[j] (doc_bounds.hip computes both from the
+// token ids). Layouts, lse format and results are those of flash_fwd / flash_bwd(mode 1); with one
+// document per sequence (doc_start = 0, doc_end = S) they are bitwise those of the plain unsplit,
+// unpipelined kernels, which the DOC instantiations extend.
+namespace {
+
+void check_doc(const at::Tensor& qk, const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t S) {
+  const long B = qk.size(0) / S;
+  for (const at::Tensor* t : {&doc_start, &doc_end}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qk.device(), "flash_doc: doc_start / doc_end must be on qk's device");
+    TORCH_CHECK(t->scalar_type() == at::kInt, "flash_doc: doc_start / doc_end must be int32");
+    TORCH_CHECK(t->is_contiguous(), "flash_doc: doc_start / doc_end must be contiguous");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S, "flash_doc: doc_start / doc_end must be [B, S]");
+  }
+}
+
+}  // namespace
+
+std::tuple<at::Tensor, at::Tensor> flash_doc_fwd(const at::Tensor& qk, const at::Tensor& qkv,
+                                                 const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t S,
+                                                 int64_t Hq, int64_t Hkv, int64_t D) {
+  check_inputs(qk, qkv, S, Hq, Hkv, D);
+  check_doc(qk, doc_start, doc_end, S);
+  const int T = qk.size(0);
+  const int B = T / S;
+  const at::DeviceGuard guard(qk.device());
+  auto out = at::empty({T, Hq * D}, qk.options());
+  auto lse = at::empty({B, Hq, (long)stat_stride(S)}, qk.options().dtype(at::kFloat));
+  if (T == 0) return {out, lse};
+  const float sl2 = LOG2E_F / std::sqrt((float)D);
+  const long ldqk = qk.size(-1);
+  const int nqt = (S + 127) / 128;
+  dim3 grid(nqt * B * Hq), block(256);
+#define FT_DOC_FWD(DD)                                                                                  \
+  hipLaunchKernelGGL((flash_fwd_kernel<E, DD, 4, 1, true>), grid, block, 0, ft_stream(), cptr<bf16_t>(qk), \
+                     cptr<bf16_t>(qkv), mptr<bf16_t>(out), mptr<float>(lse), B, (int)S, (int)Hq, (int)Hkv, \
+                     sl2, ldqk, cptr<int>(doc_start))
+  FT_DISPATCH_E16(qk.scalar_type(), {
+    if (D == 128) FT_DOC_FWD(128); else FT_DOC_FWD(64);
+  });
+#undef FT_DOC_FWD
+  FT_LAUNCH_CHECK();
+  return {out, lse};
+}
+
+// The deterministic backward (flash_bwd mode 1) with the document mask: the unsplit dQ kernel (it
+// forms delta), the unsplit slice-pair dK/dV kernel, then — with GQA — the finalize pass; without
+// GQA the dK/dV kernel stores into dqkv directly. cos / sin: dQ / dK rotated back as in flash_bwd.
+at::Tensor flash_doc_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv,
+                         const at::Tensor& out, const at::Tensor& lse, const at::Tensor& doc_start,
+                         const at::Tensor& doc_end, int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
+                         const std::optional<at::Tensor>& cos_t, const std::optional<at::Tensor>& sin_t) {
+  check_inputs(qk, qkv, S, Hq, Hkv, D);
+  check_doc(qk, doc_start, doc_end, S);
+  FT_CHECK_CONTIG(dout);
+  FT_CHECK_CONTIG(out);
+  TORCH_CHECK(dout.scalar_type() == qk.scalar_type() && out.scalar_type() == qk.scalar_type(),
+              "flash_doc_bwd: dout / out dtype");
+  const int T = qk.size(0);
+  const int B = T / S;
+  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, "flash_doc_bwd: o shape");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (long)B * Hq * stat_stride(S),
+              "flash_doc_bwd: lse shape");
+  const at::DeviceGuard guard(qk.device());
+  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
+  if (T == 0) return dqkv;
+  auto delta = at::empty({B, Hq, (long)stat_stride(S)}, qk.options().dtype(at::kFloat));
+  const int nw = waves_per_block(S, B, Hq, D);
+  const bool direct = Hq == Hkv;  // no GQA: dK / dV straight into dqkv
+  at::Tensor dk_part = direct ? at::Tensor() : at::empty({T, Hq * D}, qk.options());
+  at::Tensor dv_part = direct ? at::Tensor() : at::empty({T, Hq * D}, qk.options());
+  bf16_t* dkp = direct ? mptr<bf16_t>(dqkv) + (long)Hq * D : mptr<bf16_t>(dk_part);
+  bf16_t* dvp = direct ? mptr<bf16_t>(dqkv) + (long)(Hq + Hkv) * D : mptr<bf16_t>(dv_part);
+  const long ldkv = direct ? (long)(Hq + 2 * Hkv) * D : (long)Hq * D;
+  const bool rope = cos_t.has_value() && cos_t->defined();
+  if (rope) {
+    TORCH_CHECK(sin_t.has_value() && sin_t->defined(), "flash_doc_bwd: cos without sin");
+    FT_CHECK_F32((*cos_t));
+    FT_CHECK_F32((*sin_t));
+    FT_CHECK_CONTIG((*cos_t));
+    FT_CHECK_CONTIG((*sin_t));
+    TORCH_CHECK(cos_t->size(0) >= S && cos_t->size(1) == D / 2 && sin_t->sizes() == cos_t->sizes(),
+                "flash_doc_bwd: rope tables must be [>= S, D / 2]");
+  }
+  const float sl2 = LOG2E_F / std::sqrt((float)D);
+  const float scale = 1.f / std::sqrt((float)D);
+  const long ldqk = qk.size(-1);
+  // the RoPE backward as in flash_bwd(mode 1): dQ in the dQ kernel's store; dK in the finalize pass
+  // (GQA) or in the dK/dV kernel's store (no GQA; flash_set_direct_rope(false): a rope_bwd_ pass)
+  const bool krot = rope && direct && g_direct_rope;
+  const bool q_rot = rope && (!direct || krot);
+  const float* dq_cos = q_rot ? cptr<float>(*cos_t) : nullptr;
+  const float* dq_sin = q_rot ? cptr<float>(*sin_t) : nullptr;
+  GqaFold fold{nullptr, mptr<bf16_t>(dqkv), rope ? cptr<float>(*cos_t) : nullptr,
+               rope ? cptr<float>(*sin_t) : nullptr, 0, q_rot ? 1 : 0, krot ? 1 : 0};
+  const dim3 grid((unsigned)(((S + 32 * nw - 1) / (32 * nw)) * B * Hq)), block(64 * nw);
+#define FT_DOC_BWD(DD, NW_)                                                                                  \
+  hipLaunchKernelGGL((flash_bwd_dq_kernel<E, DD, NW_, 1, true>), grid, block, 0, ft_stream(), cptr<bf16_t>(dout), \
+                     cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse), mptr<float>(delta),              \
+                     mptr<bf16_t>(dqkv), B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk, cptr<bf16_t>(out),  \
+                     dq_cos, dq_sin, nullptr, nullptr, cptr<int>(doc_start));                                \
+  hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, DD, NW_, 1, false, true>), grid, block, 0, ft_stream(),      \
+                     cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse),              \
+                     cptr<float>(delta), dkp, dvp, ldkv, B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk,     \
+                     fold, nullptr, cptr<int>(doc_end))
+  FT_DISPATCH_E16(qk.scalar_type(), {
+    if (D == 128) {
+      FT_DOC_BWD(128, 4);
+    } else if (nw == 2) {
+      FT_DOC_BWD(64, 2);
+    } else {
+      FT_DOC_BWD(64, 4);
+    }
+  });
+#undef FT_DOC_BWD
+  FT_LAUNCH_CHECK();
+  if (direct) {
+    if (rope && !krot) rope_bwd_(dqkv, *cos_t, *sin_t, S, Hq, Hkv, D);
+    return dqkv;
+  }
+  const long vec = (long)T * ((Hq + 2 * Hkv) * D / 4);
+  const int fin_blocks = (int)std::max(1L, std::min((vec + 255) / 256, 4096L));
+  FT_DISPATCH_E16(qk.scalar_type(),
+                  hipLaunchKernelGGL((flash_bwd_finalize_kernel<E>), dim3(fin_blocks), dim3(256), 0, ft_stream(),
+                                     nullptr, cptr<bf16_t>(dk_part), cptr<bf16_t>(dv_part), mptr<bf16_t>(dqkv),
+                                     (long)T, (int)Hq, (int)Hkv, (int)D, rope ? cptr<float>(*cos_t) : nullptr,
+                                     rope ? cptr<float>(*sin_t) : nullptr, (int)S, q_rot ? 1 : 0));
+  FT_LAUNCH_CHECK();
+  return dqkv;
+}
+
 // Same-process A/B switch: slice-pair dK/dV kernel vs flash_bwd_kernel<D, 1>.
 void flash_set_dkdv2(bool on) { g_dkdv2 = on; }
 // Same-process A/B switch of the forward key split: -1 auto, 0 off, 1 on.
@@ -2089,4 +2317,12 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
       "flash_bwd(Tensor dout, Tensor qk, Tensor qkv, Tensor out, Tensor lse, int S, int Hq, int "
       "Hkv, int D, int mode=0, Tensor? cos=None, Tensor? sin=None) -> Tensor",
       &flash_bwd);
+  m.def(
+      "flash_doc_fwd(Tensor qk, Tensor qkv, Tensor doc_start, Tensor doc_end, int S, int Hq, int Hkv, int D) -> "
+      "(Tensor, Tensor)",
+      &flash_doc_fwd);
+  m.def(
+      "flash_doc_bwd(Tensor dout, Tensor qk, Tensor qkv, Tensor out, Tensor lse, Tensor doc_start, Tensor doc_end, "
+      "int S, int Hq, int Hkv, int D, Tensor? cos=None, Tensor? sin=None) -> Tensor",
+      &flash_doc_bwd);
 }

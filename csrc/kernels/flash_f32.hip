@@ -89,12 +89,18 @@ __device__ __forceinline__ void map_block(int L, int nt, int B, int H, int& t, i
   h = rem % H;
 }
 
-template <int D>
+// DOC (flash_f32_doc_*): document-masked attention for packed sequences — query i sees the keys
+// doc_start[i] <= j <= i, key j is seen by the queries j <= i < doc_end[j] (both [B, S] int32,
+// non-decreasing per sequence; doc_bounds.hip). The query-major kernels start their key loop at the
+// tile of the block's first row's doc_start, the key-major kernel ends its query loop at doc_end of
+// the tile's last key; the values only bound loops (clamped to the causal range) and feed compares.
+template <int D, bool DOC = false>
 __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(const float* __restrict__ qk,
                                                           const float* __restrict__ qkv,
                                                           float* __restrict__ out,
                                                           float* __restrict__ lse, int B, int S,
-                                                          int Hq, int Hkv, float scale, long ldqk) {
+                                                          int Hq, int Hkv, float scale, long ldqk,
+                                                          const int* __restrict__ doc_start = nullptr) {
   constexpr int DS = D / 4;
   __shared__ __attribute__((aligned(16))) float ks[TR * D];
   __shared__ __attribute__((aligned(16))) float vs[TR * D];
@@ -112,7 +118,12 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(const float* __restric
   for (int i = 0; i < DS; ++i) o[i] = 0.f;
   float m = -INFINITY, l = 0.f;
   const int kend = min((qt + 1) * TR, S);
-  for (int k0 = 0; k0 < kend; k0 += TR) {
+  int kbeg = 0, dsq = 0;
+  if constexpr (DOC) {
+    dsq = doc_start[(long)b * S + min(q, S - 1)];
+    kbeg = max(0, min(doc_start[(long)b * S + min(qt * TR, S - 1)] / TR * TR, kend));
+  }
+  for (int k0 = kbeg; k0 < kend; k0 += TR) {
     __syncthreads();
     stage<D>(ks, Kg, ldqk, k0, S);
     stage<D>(vs, Vg, ldv, k0, S);
@@ -123,7 +134,7 @@ __global__ __launch_bounds__(NT) void attn_f32_fwd_kernel(const float* __restric
     for (int j = 0; j < TR; ++j) {
       float x = quad_sum(dot_part<DS>(qv, ks + j * D + sub * DS)) * scale;
       const int key = k0 + j;
-      if (key > q || key >= S) x = -INFINITY;
+      if (key > q || key >= S || (DOC && key < dsq)) x = -INFINITY;
       s[j] = x;
       mx = fmaxf(mx, x);
     }
@@ -171,11 +182,11 @@ __global__ __launch_bounds__(NT) void attn_f32_delta_kernel(const float* __restr
 }
 
 // dQ[q] = scale * sum_keys dS[q, key] K[key],  dS = P (dP - delta),  P = exp(s - lse)
-template <int D>
+template <int D, bool DOC = false>
 __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(
     const float* __restrict__ dO, const float* __restrict__ qk, const float* __restrict__ qkv,
     const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dqkv, int B,
-    int S, int Hq, int Hkv, float scale, long ldqk) {
+    int S, int Hq, int Hkv, float scale, long ldqk, const int* __restrict__ doc_start = nullptr) {
   constexpr int DS = D / 4;
   __shared__ __attribute__((aligned(16))) float ks[TR * D];
   __shared__ __attribute__((aligned(16))) float vs[TR * D];
@@ -195,7 +206,12 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(
   const float lq = lse[((long)b * Hq + h) * S + qc];
   const float dl = delta[((long)b * Hq + h) * S + qc];
   const int kend = min((qt + 1) * TR, S);
-  for (int k0 = 0; k0 < kend; k0 += TR) {
+  int kbeg = 0, dsq = 0;
+  if constexpr (DOC) {
+    dsq = doc_start[(long)b * S + qc];
+    kbeg = max(0, min(doc_start[(long)b * S + min(qt * TR, S - 1)] / TR * TR, kend));
+  }
+  for (int k0 = kbeg; k0 < kend; k0 += TR) {
     __syncthreads();
     stage<D>(ks, Kg, ldqk, k0, S);
     stage<D>(vs, Vg, ldv, k0, S);
@@ -206,7 +222,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(
       const float s = quad_sum(dot_part<DS>(qv, kr)) * scale;
       const float dp = quad_sum(dot_part<DS>(dov, vs + j * D + sub * DS));
       const int key = k0 + j;
-      const float p = (key > q || key >= S) ? 0.f : expf(s - lq);
+      const float p = (key > q || key >= S || (DOC && key < dsq)) ? 0.f : expf(s - lq);
       axpy_part<DS>(dq, p * (dp - dl), kr);
     }
   }
@@ -214,15 +230,17 @@ __global__ __launch_bounds__(NT) void attn_f32_dq_kernel(
 }
 
 // dK[key] = scale * sum_{h in group, q} dS[q, key] Q[q],  dV[key] = sum_{h in group, q} P[q, key] dO[q]
-template <int D>
+template <int D, bool DOC = false>
 __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(
     const float* __restrict__ dO, const float* __restrict__ qk, const float* __restrict__ qkv,
     const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dqkv, int B,
-    int S, int Hq, int Hkv, float scale, long ldqk) {
+    int S, int Hq, int Hkv, float scale, long ldqk, const int* __restrict__ doc_start = nullptr,
+    const int* __restrict__ doc_end = nullptr) {
   constexpr int DS = D / 4;
   __shared__ __attribute__((aligned(16))) float qs[TR * D];
   __shared__ __attribute__((aligned(16))) float ds_[TR * D];
   __shared__ float ls[TR], dls[TR];
+  __shared__ int dss[DOC ? TR : 1];  // DOC: doc_start of the staged query rows
   int kt, b, kvh;
   map_block(blockIdx.x, (S + TR - 1) / TR, B, Hkv, kt, b, kvh);
   const int G = Hq / Hkv;
@@ -234,13 +252,15 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(
   ld_part<DS>(qkv + ((long)b * S + kc) * ldv + (long)(Hq + Hkv + kvh) * D + sub * DS, vv);
 #pragma unroll
   for (int i = 0; i < DS; ++i) dk[i] = dv[i] = 0.f;
+  int qend = S;  // DOC: no query at or behind doc_end of the tile's last valid key sees the tile
+  if constexpr (DOC) qend = max(0, min(doc_end[(long)b * S + min(kt * TR + TR, S) - 1], S));
   for (int g = 0; g < G; ++g) {  // fixed order over the GQA group: deterministic
     const int h = kvh * G + g;
     const float* Qg = qk + (long)b * S * ldqk + (long)h * D;
     const float* dOg = dO + (long)b * S * ldo + (long)h * D;
     const float* lg = lse + ((long)b * Hq + h) * S;
     const float* dg = delta + ((long)b * Hq + h) * S;
-    for (int q0 = kt * TR; q0 < S; q0 += TR) {
+    for (int q0 = kt * TR; q0 < qend; q0 += TR) {
       __syncthreads();
       stage<D>(qs, Qg, ldqk, q0, S);
       stage<D>(ds_, dOg, ldo, q0, S);
@@ -248,6 +268,7 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(
         const int qq = min(q0 + (int)threadIdx.x, S - 1);
         ls[threadIdx.x] = lg[qq];
         dls[threadIdx.x] = dg[qq];
+        if constexpr (DOC) dss[threadIdx.x] = doc_start[(long)b * S + qq];
       }
       __syncthreads();
       const int n = min(TR, S - q0);
@@ -258,7 +279,9 @@ __global__ __launch_bounds__(NT) void attn_f32_dkdv_kernel(
         const float s = quad_sum(dot_part<DS>(kv, qr)) * scale;
         const float dp = quad_sum(dot_part<DS>(vv, dr));
         const int q = q0 + i;
-        const float p = key > q ? 0.f : expf(s - ls[i]);
+        bool off = key > q;
+        if constexpr (DOC) off = off || dss[i] > key;
+        const float p = off ? 0.f : expf(s - ls[i]);
         axpy_part<DS>(dv, p, dr);
         axpy_part<DS>(dk, p * (dp - dls[i]), qr);
       }
@@ -283,6 +306,17 @@ void check_f32(const at::Tensor& qk, const at::Tensor& qkv, int64_t S, int64_t H
   TORCH_CHECK(qk.size(-1) == (Hq + Hkv) * D || qk.size(-1) == (Hq + 2 * Hkv) * D, "flash_f32: qk width");
   TORCH_CHECK(qkv.size(-1) == (Hq + 2 * Hkv) * D, "flash_f32: qkv width");
   TORCH_CHECK(qk.size(0) == qkv.size(0) && qk.size(0) % S == 0, "flash_f32: rows");
+}
+
+void check_f32_doc(const at::Tensor& qk, const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t S) {
+  const long B = qk.size(0) / S;
+  for (const at::Tensor* t : {&doc_start, &doc_end}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qk.device(), "flash_f32_doc: doc_start / doc_end must be on qk's device");
+    TORCH_CHECK(t->scalar_type() == at::kInt, "flash_f32_doc: doc_start / doc_end must be int32");
+    TORCH_CHECK(t->is_contiguous(), "flash_f32_doc: doc_start / doc_end must be contiguous");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S,
+                "flash_f32_doc: doc_start / doc_end must be [B, S]");
+  }
 }
 
 }  // namespace
@@ -350,7 +384,83 @@ at::Tensor flash_f32_bwd(const at::Tensor& dout, const at::Tensor& qk, const at:
   return dqkv;
 }
 
+// flash_f32_fwd / flash_f32_bwd with the document mask (see attn_f32_fwd_kernel).
+std::tuple<at::Tensor, at::Tensor> flash_f32_doc_fwd(const at::Tensor& qk, const at::Tensor& qkv,
+                                                     const at::Tensor& doc_start, const at::Tensor& doc_end,
+                                                     int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
+  check_f32(qk, qkv, S, Hq, Hkv, D);
+  check_f32_doc(qk, doc_start, doc_end, S);
+  const int T = qk.size(0), B = T / S;
+  const at::DeviceGuard guard(qk.device());
+  auto out = at::empty({T, Hq * D}, qk.options());
+  auto lse = at::empty({B, Hq, S}, qk.options());
+  const float scale = 1.f / std::sqrt((float)D);
+  const dim3 grid(((S + TR - 1) / TR) * B * Hq);
+  if (T > 0) {
+    if (D == 128)
+      hipLaunchKernelGGL((attn_f32_fwd_kernel<128, true>), grid, dim3(NT), 0, ft_stream(), cptr<float>(qk),
+                         cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, (int)S, (int)Hq,
+                         (int)Hkv, scale, (long)qk.size(-1), cptr<int>(doc_start));
+    else
+      hipLaunchKernelGGL((attn_f32_fwd_kernel<64, true>), grid, dim3(NT), 0, ft_stream(), cptr<float>(qk),
+                         cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, (int)S, (int)Hq,
+                         (int)Hkv, scale, (long)qk.size(-1), cptr<int>(doc_start));
+    FT_LAUNCH_CHECK();
+  }
+  return {out, lse};
+}
+
+at::Tensor flash_f32_doc_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv,
+                             const at::Tensor& out, const at::Tensor& lse, const at::Tensor& doc_start,
+                             const at::Tensor& doc_end, int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
+  check_f32(qk, qkv, S, Hq, Hkv, D);
+  check_f32_doc(qk, doc_start, doc_end, S);
+  FT_CHECK_F32(dout);
+  FT_CHECK_F32(out);
+  FT_CHECK_F32(lse);
+  FT_CHECK_CONTIG(dout);
+  FT_CHECK_CONTIG(out);
+  const int T = qk.size(0), B = T / S;
+  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, "flash_f32_doc_bwd: o shape");
+  TORCH_CHECK(lse.numel() == (long)B * Hq * S, "flash_f32_doc_bwd: lse shape");
+  const at::DeviceGuard guard(qk.device());
+  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
+  if (T == 0) return dqkv;
+  auto delta = at::empty({B, Hq, S}, qk.options());
+  const float scale = 1.f / std::sqrt((float)D);
+  const long ldqk = qk.size(-1);
+  const int nt = (S + TR - 1) / TR;
+  const int pre = (int)(((long)T * Hq * 4 + NT - 1) / NT);
+#define FT_F32_DOC_BWD(DD)                                                                           \
+  hipLaunchKernelGGL(attn_f32_delta_kernel<DD>, dim3(pre), dim3(NT), 0, ft_stream(), cptr<float>(dout), \
+                     cptr<float>(out), mptr<float>(delta), B, (int)S, (int)Hq);                      \
+  hipLaunchKernelGGL((attn_f32_dq_kernel<DD, true>), dim3(nt * B * Hq), dim3(NT), 0, ft_stream(),    \
+                     cptr<float>(dout), cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse),         \
+                     cptr<float>(delta), mptr<float>(dqkv), B, (int)S, (int)Hq, (int)Hkv, scale, ldqk, \
+                     cptr<int>(doc_start));                                                          \
+  hipLaunchKernelGGL((attn_f32_dkdv_kernel<DD, true>), dim3(nt * B * Hkv), dim3(NT), 0, ft_stream(), \
+                     cptr<float>(dout), cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse),         \
+                     cptr<float>(delta), mptr<float>(dqkv), B, (int)S, (int)Hq, (int)Hkv, scale, ldqk, \
+                     cptr<int>(doc_start), cptr<int>(doc_end))
+  if (D == 128) {
+    FT_F32_DOC_BWD(128);
+  } else {
+    FT_F32_DOC_BWD(64);
+  }
+#undef FT_F32_DOC_BWD
+  FT_LAUNCH_CHECK();
+  return dqkv;
+}
+
 TORCH_LIBRARY_FRAGMENT(ftamd, m) {
+  m.def(
+      "flash_f32_doc_fwd(Tensor qk, Tensor qkv, Tensor doc_start, Tensor doc_end, int S, int Hq, int Hkv, int D) "
+      "-> (Tensor, Tensor)",
+      &flash_f32_doc_fwd);
+  m.def(
+      "flash_f32_doc_bwd(Tensor dout, Tensor qk, Tensor qkv, Tensor out, Tensor lse, Tensor doc_start, Tensor "
+      "doc_end, int S, int Hq, int Hkv, int D) -> Tensor",
+      &flash_f32_doc_bwd);
   m.def("flash_f32_fwd(Tensor qk, Tensor qkv, int S, int Hq, int Hkv, int D) -> (Tensor, Tensor)",
         &flash_f32_fwd);
   m.def(

@@ -132,12 +132,13 @@ class TransformerBlock(nn.Module):
         self.layernorm = a.norm_type == "layernorm"
         self.attn_keep = Fx.AttentionKeep()
 
-    def forward(self, h, d, cos, sin, seq_len, gen=None):
+    def forward(self, h, d, cos, sin, seq_len, gen=None, doc=None):
         """Pre-norm block (reference model.py:310-311) on the residual stream ``h`` with the
         previous block's pending output ``d`` (its add is fused into this block's first norm).
         Returns (h', d') with the block output h' + d' still to be added. ``gen``: the model's
         forward generation when this block is recomputed in backward with its attention output
-        kept (selective checkpointing); None otherwise."""
+        kept (selective checkpointing); None otherwise. ``doc``: (doc_start, doc_end) of the
+        document mask (:meth:`Transformer.set_document_mask`) or None."""
         at, ff = self.attention, self.feed_forward
         sk = lambda p: getattr(p, "_ft_sink", None)  # noqa: E731
         if d is None:
@@ -146,7 +147,8 @@ class TransformerBlock(nn.Module):
             h, xn = Fx.add_norm(h, d, self.attention_norm.weight, sk(self.attention_norm.weight), self.eps,
                                 self.layernorm)
         o = Fx.qkv_rope_attention(xn, at.wqkv, at.wqkv_sink, cos, sin, seq_len, at.n_heads, at.n_kv_heads,
-                                  at.head_dim, self.attn_keep if gen is not None else None, -1 if gen is None else gen)
+                                  at.head_dim, self.attn_keep if gen is not None else None, -1 if gen is None else gen,
+                                  doc)
         da = Fx.linear(o.view(*h.shape[:-1], -1), at.wo.weight, sk(at.wo.weight))
         h, hn = Fx.add_norm(h, da, self.ffn_norm.weight, sk(self.ffn_norm.weight), self.eps, self.layernorm)
         return h, Fx.feed_forward(hn, ff.w13, ff.w2.weight, ff.w13_sink, sk(ff.w2.weight))
@@ -172,6 +174,15 @@ class Transformer(nn.Module):
         self.recompute_layers = 0  # activation checkpointing: blocks [0, n) recompute in backward
         self.recompute_attention = False  # False: recomputed blocks keep their attention output
         self._gen = 0  # forward generation (tags kept attention outputs)
+        self.doc_bos: Optional[int] = None  # document mask: the token id that starts a document
+
+    def set_document_mask(self, bos_id: Optional[int]) -> None:
+        """Attention within each packed document only: every ``bos_id`` token starts a document and
+        query i sees the keys from its document's BOS up to i (None: plain causal attention, the
+        default and the reference's behaviour). The boundaries are derived from ``tokens`` in
+        ``forward`` (ops.attention.doc_bounds: one scan kernel on the GPU) and passed to every
+        block; RoPE positions are not reset per document (rotary scores depend on i - j only)."""
+        self.doc_bos = None if bos_id is None else int(bos_id)
 
     def set_activation_checkpointing(self, n_layers: int, recompute_attention: bool = False) -> None:
         """Recompute the first ``n_layers`` blocks (-1: all) during backward instead of keeping
@@ -270,6 +281,7 @@ class Transformer(nn.Module):
         self._wait(emb_r)
         h = Fx.embedding(tokens, self.tok_embeddings.weight, sk(self.tok_embeddings.weight))
         cos, sin = self.rope_cos, self.rope_sin
+        doc = None if self.doc_bos is None else Fx.doc_bounds(tokens, self.doc_bos)
         d = None
         self._gen += 1
         gen = None if self.recompute_attention else self._gen
@@ -279,9 +291,9 @@ class Transformer(nn.Module):
                 # non-reentrant: the custom Functions' saved tensors are dropped and regenerated
                 # by re-running the block (deterministic kernels → bit-identical gradients);
                 # with ``gen`` the re-run reuses the kept attention output
-                h, d = torch.utils.checkpoint.checkpoint(layer, h, d, cos, sin, S, gen, use_reentrant=False)
+                h, d = torch.utils.checkpoint.checkpoint(layer, h, d, cos, sin, S, gen, doc, use_reentrant=False)
             else:
-                h, d = layer(h, d, cos, sin, S)
+                h, d = layer(h, d, cos, sin, S, None, doc)
         self._wait(final_r)
         a = self.model_args
         ln = a.norm_type == "layernorm"

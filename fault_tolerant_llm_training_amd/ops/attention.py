@@ -34,21 +34,53 @@ def set_deterministic(flag: bool) -> None:
     _BWD_MODE = 1 if flag else 0
 
 
-def flash_attn_fwd(qk, qkv, S, hq, hkv, d):
+def doc_bounds(tokens: torch.Tensor, bos: int):
+    """Document boundaries of packed sequences. tokens: [B, S] integer ids; a document starts at
+    every ``bos``. Returns int32 ``(doc_start, doc_end)`` [B, S]: ``doc_start[i]`` = position of
+    the most recent BOS at or before ``i`` (0 if none), ``doc_end[i]`` = position of the next BOS
+    after ``i`` (S if none). Query ``i`` sees key ``j`` iff ``doc_start[i] <= j <= i``. On the GPU
+    one scan kernel (csrc/kernels/doc_bounds.hip; no host sync, graph-capturable); elsewhere the
+    same scans composed from cummax / cummin."""
+    if tokens.is_cuda:
+        return tuple(kernels().doc_bounds(tokens.long().contiguous(), int(bos)))
+    B, S = tokens.shape
+    pos = torch.arange(S, device=tokens.device).expand(B, S)
+    is_bos = tokens == bos
+    start = torch.where(is_bos, pos, torch.zeros_like(pos)).cummax(dim=1).values
+    # next BOS strictly after i: a reversed running minimum, shifted by one
+    nxt = torch.where(is_bos, pos, torch.full_like(pos, S)).flip(1).cummin(dim=1).values.flip(1)
+    end = torch.cat([nxt[:, 1:], torch.full_like(pos[:, :1], S)], dim=1)
+    return start.to(torch.int32), end.to(torch.int32)
+
+
+def flash_attn_fwd(qk, qkv, S, hq, hkv, d, doc=None):
     """Returns (o [T, Hq*D], lse [B, Hq, S'] fp32) in the model dtype. The HIP kernels only, no
     fallback (``kernels()`` raises if the extension is missing): the MFMA kernels for bf16 / fp16
-    (csrc/kernels/flash_attn.hip), the fp32 vector-ALU kernels for fp32 models (flash_f32.hip)."""
+    (csrc/kernels/flash_attn.hip), the fp32 vector-ALU kernels for fp32 models (flash_f32.hip).
+    ``doc = (doc_start, doc_end)`` (:func:`doc_bounds`): the document-masked kernels."""
+    if doc is not None:
+        if qk.dtype == torch.float32:
+            return tuple(kernels().flash_f32_doc_fwd(qk, qkv, doc[0], doc[1], S, hq, hkv, d))
+        return tuple(kernels().flash_doc_fwd(qk, qkv, doc[0], doc[1], S, hq, hkv, d))
     if qk.dtype == torch.float32:
         return tuple(kernels().flash_f32_fwd(qk, qkv, S, hq, hkv, d))
     return tuple(kernels().flash_fwd(qk, qkv, S, hq, hkv, d))
 
 
-def flash_attn_bwd(do, qk, qkv, o, lse, S, hq, hkv, d, cos=None, sin=None):
+def flash_attn_bwd(do, qk, qkv, o, lse, S, hq, hkv, d, cos=None, sin=None, doc=None):
     """Returns dqkv [T, (Hq+2Hkv)*D]. With ``cos`` / ``sin`` the dQ / dK columns are rotated back
     (RoPE backward, reference model.py:100-126): the gradient of the UNROTATED projection — on the
     16-bit path inside the kernel pass that folds the GQA dK / dV partials (no separate RoPE
     pass); without them dQ / dK stay in the rotated frame. Both variants are deterministic (fp32:
-    always; bf16 / fp16: unless FT_FLASH_BWD_MODE=0)."""
+    always; bf16 / fp16: unless FT_FLASH_BWD_MODE=0). ``doc``: the document-masked kernels
+    (deterministic only)."""
+    if doc is not None:
+        if qk.dtype == torch.float32:
+            dqkv = kernels().flash_f32_doc_bwd(do, qk, qkv, o, lse, doc[0], doc[1], S, hq, hkv, d)
+            if cos is not None:
+                kernels().rope_bwd_(dqkv, cos, sin, S, hq, hkv, d)
+            return dqkv
+        return kernels().flash_doc_bwd(do, qk, qkv, o, lse, doc[0], doc[1], S, hq, hkv, d, cos, sin)
     if qk.dtype == torch.float32:
         dqkv = kernels().flash_f32_bwd(do, qk, qkv, o, lse, S, hq, hkv, d)
         if cos is not None:
@@ -72,8 +104,10 @@ def rope_reference(x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor) -> tor
     return out.type_as(x)
 
 
-def attention_reference(qkv, cos, sin, seq_len, hq, hkv, d):
-    """Reference math: RoPE → repeat_kv → causal SDPA (model.py:179-215). qkv: [B*S, W]."""
+def attention_reference(qkv, cos, sin, seq_len, hq, hkv, d, doc_start=None):
+    """Reference math: RoPE → repeat_kv → causal SDPA (model.py:179-215). qkv: [B*S, W].
+    ``doc_start`` [B, S]: the document mask (query i sees doc_start[i] <= j <= i) as a boolean
+    SDPA mask instead of ``is_causal``."""
     T = qkv.shape[0]
     B = T // seq_len
     q = qkv[:, : hq * d].reshape(B, seq_len, hq, d)
@@ -85,7 +119,13 @@ def attention_reference(qkv, cos, sin, seq_len, hq, hkv, d):
     if rep > 1:
         k = k.repeat_interleave(rep, dim=2)
         v = v.repeat_interleave(rep, dim=2)
-    o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
+    if doc_start is None:
+        o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), is_causal=True)
+    else:
+        pos = torch.arange(seq_len, device=qkv.device)
+        mask = (pos.view(1, 1, -1) <= pos.view(1, -1, 1)) & (pos.view(1, 1, -1) >= doc_start.view(B, -1, 1))
+        o = F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+                                           attn_mask=mask.view(B, 1, seq_len, seq_len))
     return o.transpose(1, 2).reshape(T, hq * d)
 
 
@@ -110,9 +150,14 @@ class RopeAttentionFn(torch.autograd.Function):
     dK/dV partials (so neither this node nor the projection's backward runs a RoPE pass)."""
 
     @staticmethod
-    def forward(ctx, qkv, cos, sin, seq_len, hq, hkv, d, keep=None, gen=-1, rotated=False):
+    def forward(ctx, qkv, cos, sin, seq_len, hq, hkv, d, keep=None, gen=-1, rotated=False, doc=None):
         ctx.cfg = (seq_len, hq, hkv, d)
         ctx.rotated = rotated
+        # (doc_start, doc_end) int32, no gradient. Kept on ctx rather than through save_for_backward
+        # on purpose: a checkpointed block is re-run with the same tensors as arguments (checkpoint
+        # holds its inputs), nothing writes them after doc_bounds made them, and as non-float
+        # side inputs they need neither the saved-tensor hooks nor version checks.
+        ctx.doc = doc
         hit = keep is not None and keep.gen == gen and keep.o is not None
         if native(qkv):
             qkv = qkv.contiguous()
@@ -121,7 +166,7 @@ class RopeAttentionFn(torch.autograd.Function):
                 o, lse = keep.o, keep.lse
                 keep.o = keep.lse = None
             else:
-                o, lse = flash_attn_fwd(qk, qkv, seq_len, hq, hkv, d)
+                o, lse = flash_attn_fwd(qk, qkv, seq_len, hq, hkv, d, doc)
                 if keep is not None:
                     keep.gen, keep.o, keep.lse = gen, o, lse
             ctx.save_for_backward(qkv, qk, o, lse, cos, sin)
@@ -131,7 +176,7 @@ class RopeAttentionFn(torch.autograd.Function):
             o = keep.o
             keep.o = None
         else:
-            o = attention_reference(qkv, cos, sin, seq_len, hq, hkv, d)
+            o = attention_reference(qkv, cos, sin, seq_len, hq, hkv, d, None if doc is None else doc[0])
             if keep is not None:
                 keep.gen, keep.o = gen, o
         return o
@@ -141,21 +186,24 @@ class RopeAttentionFn(torch.autograd.Function):
         seq_len, hq, hkv, d = ctx.cfg
         if native(do):
             qkv, qk, o, lse, cos, sin = ctx.saved_tensors
-            dqkv = flash_attn_bwd(do.contiguous(), qk, qkv, o, lse, seq_len, hq, hkv, d, cos, sin)
-            return dqkv, None, None, None, None, None, None, None, None, None
+            dqkv = flash_attn_bwd(do.contiguous(), qk, qkv, o, lse, seq_len, hq, hkv, d, cos, sin, ctx.doc)
+            return dqkv, None, None, None, None, None, None, None, None, None, None
         qkv, cos, sin = ctx.saved_tensors
         with torch.enable_grad():
             x = qkv.detach().requires_grad_(True)
-            o = attention_reference(x, cos, sin, seq_len, hq, hkv, d)
+            o = attention_reference(x, cos, sin, seq_len, hq, hkv, d, None if ctx.doc is None else ctx.doc[0])
             (dx,) = torch.autograd.grad(o, (x,), do)
-        return dx, None, None, None, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None, None, None, None
 
 
 def rope_attention(qkv, cos, sin, seq_len, hq, hkv, d, keep: Optional[AttentionKeep] = None, gen: int = -1,
-                   rotated: bool = False):
+                   rotated: bool = False, doc=None):
     """RoPE on the packed projection, then causal GQA attention. ``keep``/``gen``: selective
-    activation checkpointing (see :class:`AttentionKeep`)."""
-    return RopeAttentionFn.apply(qkv, cos, sin, seq_len, hq, hkv, d, keep, gen, rotated)
+    activation checkpointing (see :class:`AttentionKeep`). ``doc = (doc_start, doc_end)``
+    (:func:`doc_bounds`): attention within each packed document only. RoPE positions stay the
+    in-sequence ones: rotary scores depend on i - j alone, so resetting them per document would
+    give the same attention."""
+    return RopeAttentionFn.apply(qkv, cos, sin, seq_len, hq, hkv, d, keep, gen, rotated, doc)
 
 
 # QKV projection with RoPE in the GEMM epilogue (csrc/kernels/gemm_w4.hip, gemm_qkv_rope_w4): the
@@ -211,14 +259,14 @@ class QKVRopeFn(torch.autograd.Function):
 
 
 def qkv_rope_attention(xn, wqkv, sink, cos, sin, seq_len, hq, hkv, d, keep: Optional[AttentionKeep] = None,
-                       gen: int = -1):
+                       gen: int = -1, doc=None):
     """QKV projection + RoPE + causal GQA attention (reference model.py:179-212). Returns o [.., Hq D]."""
     x2 = xn.reshape(-1, xn.shape[-1])
     if _qkv_rope_ok(x2, wqkv, d):
         qkv = QKVRopeFn.apply(x2.contiguous(), wqkv, sink, cos, sin, seq_len, hq, hkv, d)
-        return rope_attention(qkv, cos, sin, seq_len, hq, hkv, d, keep, gen, rotated=True)
+        return rope_attention(qkv, cos, sin, seq_len, hq, hkv, d, keep, gen, rotated=True, doc=doc)
     qkv = Fx.linear(xn, wqkv, sink)
-    return rope_attention(qkv.view(-1, qkv.shape[-1]), cos, sin, seq_len, hq, hkv, d, keep, gen)
+    return rope_attention(qkv.view(-1, qkv.shape[-1]), cos, sin, seq_len, hq, hkv, d, keep, gen, doc=doc)
 
 
 # functional.py re-exports this module's names at its end and this module calls into functional at

@@ -846,6 +846,7 @@ from .attention import (  # noqa: E402,F401
     QKVRopeFn,
     RopeAttentionFn,
     attention_reference,
+    doc_bounds,
     qkv_rope_attention,
     rope_attention,
     rope_reference,

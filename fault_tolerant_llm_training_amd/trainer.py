@@ -190,6 +190,7 @@ def _build_source(args, info, tokenizer_vocab_holder: Dict[str, Any]):
     if args.synthetic_data:
         vocab = args.vocab_size or SYNTHETIC_VOCAB
         tokenizer_vocab_holder["vocab"] = vocab
+        tokenizer_vocab_holder["bos"] = 1  # no tokenizer: the fallback id below (--document-mask)
         ds = SyntheticTokens(vocab, S, seed=args.seed, rank=info.rank, world_size=info.world_size, pin=False)
         return SyntheticSource(ds, B)
     from .data.parquet import CollatorForCLM, IterableParquetDataset, ParquetDataset
@@ -197,8 +198,9 @@ def _build_source(args, info, tokenizer_vocab_holder: Dict[str, Any]):
 
     tok = load_tokenizer(args.tokenizer_name_or_path)
     tokenizer_vocab_holder["vocab"] = args.vocab_size or int(tok.vocab_size)
+    bos = getattr(tok, "bos_token_id", None)
+    tokenizer_vocab_holder["bos"] = 1 if bos is None else int(bos)
     if args.iterable_dataset:
-        bos = getattr(tok, "bos_token_id", None)
         ds = IterableParquetDataset(args.dataset, tok, S, bos_token_id=1 if bos is None else int(bos),
                                     rank=info.rank, world_size=info.world_size)
         return IterableSource(ds, B)
@@ -277,6 +279,10 @@ def train(args) -> int:
         model.set_activation_checkpointing(args.activation_checkpointing,
                                            recompute_attention=getattr(args, "recompute_attention", False))
         logger.info(f"Activation checkpointing: recomputing {model.recompute_layers} of {model.n_layers} blocks")
+    if getattr(args, "document_mask", False):
+        model.set_document_mask(holder["bos"])
+        logger.info(f"Document mask: on -- attention stays within each packed document; token id {holder['bos']} "
+                    "(BOS) starts a document (the logged MFU still counts causal-half attention FLOPs)")
     if checkpoint is not None:
         restore_model(model, checkpoint["model"])
         logger.info("Model loaded from checkpoint")

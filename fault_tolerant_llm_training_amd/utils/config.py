@@ -240,6 +240,13 @@ def build_parser() -> argparse.ArgumentParser:
         "(default keeps each recomputed block's attention output: one T x Hq x D tensor per block)",
     )
     parser.add_argument(
+        "--document-mask",
+        action="store_true",
+        help="Attention within each packed document only: every BOS token (the tokenizer's id, 1 if it has "
+        "none) starts a document and a token attends from its document's BOS up to itself (default: plain "
+        "causal attention across the whole sample, as the reference)",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
