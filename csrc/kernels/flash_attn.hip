@@ -1844,11 +1844,9 @@ int g_dq_split = -1;
 // dK/dV split of the slice-pair kernel: -1 auto, 0 off, 1 on (flash_set_kv_split, for A/B).
 int g_kv_split = -1;
 
-// Deterministic backward, dK/dV stage: the slice-pair kernel (default) or the one-slice
-// flash_bwd_kernel<D, 1> (flash_set_dkdv2, for A/B); the slice-pair kernel also for head_dim 64:
-// g_dkdv2_64 (measured slower there, off).
+// Deterministic backward, dK/dV stage at head_dim 128: the slice-pair kernel (default) or the
+// one-slice flash_bwd_kernel<D, 1> (flash_set_dkdv2, for A/B).
 bool g_dkdv2 = true;
-bool g_dkdv2_64 = false;
 
 // GQA fold of the deterministic backward in the separate finalize pass (default) or inside the
 // dK/dV kernel by each key tile's last q-head block (flash_set_bwd_fold).
@@ -1858,9 +1856,6 @@ bool g_dkdv2_64 = false;
 // as a 128-block tail behind the heaviest key tiles (profiles/r4_flash_gqa_fold_probe.log).
 bool g_bwd_fold = false;
 
-// No-GQA backward (GPT-2-sized presets): dQ rotated in the dQ kernel's store and dK in the dK/dV
-// kernel's, so no separate rope_bwd_ pass (3 kernels per layer); flash_set_direct_rope(false): the
-// pass after the two kernels (A/B).
 // GQA deterministic backward in 3 kernels (FT_FLASH_FOLD3=1 / flash_set_fold3(true)): the dK/dV
 // kernel first, forming delta itself from O (SD), then the dQ kernel, which also folds the GQA
 // partials (no finalize pass). Bitwise equal to the default 4-kernel order (dQ, dK/dV, finalize) but
@@ -1872,6 +1867,9 @@ bool g_fold3 = [] {
   return e != nullptr && std::atoi(e) != 0;
 }();
 
+// No-GQA backward (GPT-2-sized presets): dQ rotated in the dQ kernel's store and dK in the dK/dV
+// kernel's, so no separate rope_bwd_ pass (3 kernels per layer); FT_FLASH_DIRECT_ROPE=0 /
+// flash_set_direct_rope(false): the pass after the two kernels (A/B).
 bool g_direct_rope = [] {
   const char* e = std::getenv("FT_FLASH_DIRECT_ROPE");
   return e == nullptr || std::atoi(e) != 0;
@@ -1901,9 +1899,7 @@ int* fold_counters(const c10::Device& dev, long n) {
 // The forward keeps 4-wave blocks (2 waves: 32.0 -> 36.6 us on GPT-2-small's layer); the
 // backward's dK/dV + dQ kernels gain (112.8 -> 94.2 us; 118.2 -> 99.2 us at 16 heads),
 // profiles/r2_flash_small_heads.log.
-static const bool g_force_nw4 = false;
 int waves_per_block(long S, long B, long Hq, long D) {
-  if (g_force_nw4) return 4;
   return (D == 64 && ((S + 127) / 128) * B * Hq < 512) ? 2 : 4;
 }
 
@@ -1924,7 +1920,296 @@ void check_inputs(const at::Tensor& qk, const at::Tensor& qkv, int64_t S, int64_
   TORCH_CHECK(qk.size(0) == qkv.size(0) && qk.size(0) % S == 0, "flash: rows");
 }
 
+// dout / out / lse of a backward op (`op`: the message prefix)
+void check_bwd(const char* op, const at::Tensor& dout, const at::Tensor& out, const at::Tensor& lse,
+               const at::Tensor& qk, int64_t S, int64_t Hq, int64_t D) {
+  FT_CHECK_CONTIG(dout);
+  FT_CHECK_CONTIG(out);
+  TORCH_CHECK(dout.scalar_type() == qk.scalar_type() && out.scalar_type() == qk.scalar_type(), op,
+              ": dout / out dtype");
+  const long T = qk.size(0);
+  TORCH_CHECK(dout.numel() == T * Hq * D && out.numel() == T * Hq * D, op, ": o shape");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == T / S * Hq * stat_stride(S), op, ": lse shape");
+}
+
+// The optional RoPE tables of a backward op: true when given (then both, fp32 [>= S, D / 2]).
+bool check_rope(const char* op, const std::optional<at::Tensor>& cos_t, const std::optional<at::Tensor>& sin_t,
+                int64_t S, int64_t D) {
+  if (!cos_t.has_value() || !cos_t->defined()) return false;
+  TORCH_CHECK(sin_t.has_value() && sin_t->defined(), op, ": cos without sin");
+  FT_CHECK_F32((*cos_t));
+  FT_CHECK_F32((*sin_t));
+  FT_CHECK_CONTIG((*cos_t));
+  FT_CHECK_CONTIG((*sin_t));
+  TORCH_CHECK(cos_t->size(0) >= S && cos_t->size(1) == D / 2 && sin_t->sizes() == cos_t->sizes(), op,
+              ": rope tables must be [>= S, D / 2]");
+  return true;
+}
+
+// ================================================================== host: forward
+struct FwdArgs {
+  const bf16_t *qk, *qkv;
+  bf16_t* out;
+  float* lse;
+  int B, S, Hq, Hkv;
+  float sl2;
+  long ldqk;
+  const int* doc_start;  // the document mask (flash_doc_fwd), else null
+};
+
+template <class E, int D>
+void launch_fwd(const FwdArgs& a, dim3 grid, bool split, bool pipe) {
+  const dim3 block(split ? 512 : 256);
+  if (a.doc_start != nullptr)
+    hipLaunchKernelGGL((flash_fwd_kernel<E, D, 4, 1, true>), grid, block, 0, ft_stream(), a.qk, a.qkv, a.out, a.lse,
+                       a.B, a.S, a.Hq, a.Hkv, a.sl2, a.ldqk, a.doc_start);
+  else if (split)
+    hipLaunchKernelGGL((flash_fwd_kernel<E, D, 4, 2>), grid, block, 0, ft_stream(), a.qk, a.qkv, a.out, a.lse, a.B,
+                       a.S, a.Hq, a.Hkv, a.sl2, a.ldqk, nullptr);
+  else if (pipe)
+    hipLaunchKernelGGL((flash_fwd_pipe_kernel<E, D, 4>), grid, block, 0, ft_stream(), a.qk, a.qkv, a.out, a.lse, a.B,
+                       a.S, a.Hq, a.Hkv, a.sl2, a.ldqk, g_fwd_prof);
+  else
+    hipLaunchKernelGGL((flash_fwd_kernel<E, D, 4, 1>), grid, block, 0, ft_stream(), a.qk, a.qkv, a.out, a.lse, a.B,
+                       a.S, a.Hq, a.Hkv, a.sl2, a.ldqk, nullptr);
+}
+
+// ================================================================== host: backward
+// Every decision of one backward, taken in plan_bwd (the only reader of the knobs above).
+struct BwdPlan {
+  int mode;       // 0: dQ by fp32 atomics in the KV-major kernel (fastest); 1: deterministic -- the Q-major
+                  // dQ kernel + a dK/dV kernel without dQ (no atomics); 2: timing experiment only (racy dQ stores)
+  int nw;         // waves per block of the deterministic dQ and slice-pair dK/dV kernels
+  bool doc;       // document mask (flash_doc_bwd)
+  bool dkdv2;     // dK/dV by the slice-pair kernel (else the one-slice flash_bwd_kernel<D, 1>)
+  bool kv_split;  // ... its split form
+  bool dq_split;  // the dQ kernel's key split
+  bool direct;    // no GQA: dK / dV stored into dqkv by the slice-pair kernel (no partials, no finalize pass)
+  int* fold;      // GQA fold inside the slice-pair kernel: its tile counters, else null
+  bool fold3;     // GQA in 3 kernels: dK/dV first (delta from O), then dQ + the fold
+  bool krot;      // RoPE backward of dK in the slice-pair kernel's direct store
+  bool q_rot;     // RoPE backward of dQ in the dQ kernel's store
+};
+
+BwdPlan plan_bwd(const c10::Device& dev, long S, long B, long Hq, long Hkv, long D, long mode, bool rope, bool doc) {
+  BwdPlan p{};
+  // the document mask is built into the unsplit deterministic kernels only
+  p.doc = doc;
+  p.mode = doc || mode == 1 ? 1 : (mode == 0 ? 0 : 2);
+  const bool det = p.mode == 1;
+  p.nw = waves_per_block(S, B, Hq, D);
+  const long tiles = (S + 32 * p.nw - 1) / (32 * p.nw);  // of the deterministic dK/dV and dQ kernels
+  // head_dim 64 with 4-wave blocks: the one-slice dK/dV kernel is faster (S = 8192, 16 heads: 631 vs
+  // 783 us, profiles/r2_flash_long_context.log); it has no document mask, so the doc backward
+  // takes the slice pair there too
+  p.dkdv2 = det && (doc || (D == 128 ? g_dkdv2 : p.nw == 2));
+  // no GQA: that kernel writes dK / dV into dqkv itself, dQ comes from the dQ kernel, so the
+  // finalize pass (and the partial buffers) are skipped
+  p.direct = p.dkdv2 && Hq == Hkv;
+  // dK/dV split, head_dim 64 only (at 128 the doubled block spills): flash_set_kv_split(0 / 1)
+  // forces; default: grids of at most one wave per SIMD
+  p.kv_split = p.dkdv2 && !doc && D == 64 && (g_kv_split >= 0 ? g_kv_split == 1 : tiles * B * Hq * p.nw <= 1024);
+  // dQ key split by default (flash_set_dq_split(0) turns it off): S = 2048, 12 heads of 64:
+  // 94 -> 83 us for the whole backward; 8B layer 173 -> 167 us; S = 16384 1006 -> 972 us
+  // (profiles/r2_flash_key_split.log)
+  p.dq_split = det && !doc && g_dq_split != 0;
+  // RoPE backward of dQ in the dQ kernel's epilogue; of dK in the pass that folds the GQA partials
+  // or -- no GQA -- in the dK/dV kernel's store, so no rope_bwd_ pass follows
+  // (flash_set_direct_rope(false) restores that pass for Q and K, for A/B)
+  p.krot = rope && p.direct && g_direct_rope;
+  p.q_rot = rope && det && (!p.direct || p.krot);
+  const bool gqa = p.dkdv2 && !p.direct && !doc;
+  // the in-kernel fold holds at most 8 q-head partials per unit (uint4 x[U][8]): wider groups
+  // take the finalize pass
+  if (gqa && g_bwd_fold && Hq / Hkv <= 8) p.fold = fold_counters(dev, B * Hkv * tiles);
+  // 3-kernel GQA backward: a column slice of D / G columns per q-head block must be whole 16-B chunks
+  p.fold3 = gqa && g_fold3 && p.fold == nullptr && D % (8 * (Hq / Hkv)) == 0;
+  return p;
+}
+
+// What the backward kernels take.
+struct BwdArgs {
+  const bf16_t *dout, *qk, *qkv, *out;
+  const float* lse;
+  float* delta;
+  float* dq_acc;                 // modes 0 / 2: the fp32 dQ accumulator, else null
+  bf16_t* dqkv;
+  bf16_t *dkp, *dvp;             // dK / dV of the kernels: the GQA partials [T, Hq D], or -- direct -- dqkv's columns
+  long ldkv;                     // their row stride
+  int B, S, Hq, Hkv;
+  float sl2, scale;
+  long ldqk;
+  GqaFold fold;
+  const float *dq_cos, *dq_sin;  // q_rot: the RoPE tables for the dQ kernel
+  const bf16_t *fkp, *fvp;       // fold3: the partials the dQ kernel folds
+  const int *doc_start, *doc_end;
+};
+
+inline dim3 det_grid(const BwdArgs& a, int nw) { return dim3(((a.S + 32 * nw - 1) / (32 * nw)) * a.B * a.Hq); }
+
+// delta = rowsum(dO * O) (modes 0 / 2; the deterministic kernels form it themselves)
+template <class E, int D>
+void launch_pre(const BwdArgs& a) {
+  const long rows = (long)a.B * a.S * a.Hq;
+  hipLaunchKernelGGL((flash_bwd_pre_kernel<E, D>), dim3((int)((rows * 16 + 255) / 256)), dim3(256), 0, ft_stream(),
+                     a.dout, a.out, a.delta, a.B, a.S, a.Hq);
+}
+
+// the one-slice KV-major kernel: DQ = 0 / 2 with dQ (atomics / racy), 1 dK / dV only
+template <class E, int D, int DQ>
+void launch_one_slice(const BwdArgs& a) {
+  hipLaunchKernelGGL((flash_bwd_kernel<E, D, DQ>), dim3(((a.S + 127) / 128) * a.B * a.Hq), dim3(256), 0, ft_stream(),
+                     a.dout, a.qk, a.qkv, a.lse, a.delta, a.dq_acc, a.dkp, a.dvp, a.B, a.S, a.Hq, a.Hkv, a.sl2,
+                     a.scale, a.ldqk);
+}
+
+template <class E, int D, int NW, int SPLIT, bool DOC>
+void launch_dq_as(const BwdArgs& a) {
+  hipLaunchKernelGGL((flash_bwd_dq_kernel<E, D, NW, SPLIT, DOC>), det_grid(a, NW), dim3(64 * NW * SPLIT), 0,
+                     ft_stream(), a.dout, a.qk, a.qkv, a.lse, a.delta, a.dqkv, a.B, a.S, a.Hq, a.Hkv, a.sl2, a.scale,
+                     a.ldqk, a.out, a.dq_cos, a.dq_sin, a.fkp, a.fvp, a.doc_start);
+}
+
+// the deterministic dQ kernel
+template <class E, int D, int NW>
+void launch_dq(const BwdPlan& p, const BwdArgs& a) {
+  if (p.doc) launch_dq_as<E, D, NW, 1, true>(a);
+  else if (p.dq_split) launch_dq_as<E, D, NW, 2, false>(a);
+  else launch_dq_as<E, D, NW, 1, false>(a);
+}
+
+template <class E, int D, int NW, int SPLIT, bool SD, bool DOC>
+void launch_dkdv2_as(const BwdArgs& a) {
+  hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, D, NW, SPLIT, SD, DOC>), det_grid(a, NW), dim3(64 * NW * SPLIT), 0,
+                     ft_stream(), a.dout, a.qk, a.qkv, a.lse, a.delta, a.dkp, a.dvp, a.ldkv, a.B, a.S, a.Hq, a.Hkv,
+                     a.sl2, a.scale, a.ldqk, a.fold, SD ? a.out : nullptr, a.doc_end);
+}
+
+// the slice-pair dK/dV kernel (SD: it forms delta itself from O, fold3)
+template <class E, int D, int NW>
+void launch_dkdv2(const BwdPlan& p, const BwdArgs& a) {
+  if (p.doc) return launch_dkdv2_as<E, D, NW, 1, false, true>(a);
+  if constexpr (D == 64 && NW == 4) {
+    TORCH_INTERNAL_ASSERT(false, "flash_bwd: head_dim 64 with 4-wave blocks takes the one-slice dK/dV kernel");
+  } else {
+    if constexpr (D == 64) {  // the split form, see plan_bwd
+      if (p.kv_split) return p.fold3 ? launch_dkdv2_as<E, D, NW, 2, true, false>(a)
+                                     : launch_dkdv2_as<E, D, NW, 2, false, false>(a);
+    }
+    p.fold3 ? launch_dkdv2_as<E, D, NW, 1, true, false>(a) : launch_dkdv2_as<E, D, NW, 1, false, false>(a);
+  }
+}
+
+// the deterministic backward's dQ and dK/dV kernels
+template <class E, int D, int NW>
+void launch_det(const BwdPlan& p, const BwdArgs& a) {
+  if (!p.dkdv2) {
+    launch_dq<E, D, NW>(p, a);
+    launch_one_slice<E, D, 1>(a);
+  } else if (p.fold3) {  // dK/dV first (it forms delta itself), dQ after it (folds the partials it wrote)
+    launch_dkdv2<E, D, NW>(p, a);
+    launch_dq<E, D, NW>(p, a);
+  } else {  // dQ first: it forms delta for the dK/dV kernel (no flash_bwd_pre pass)
+    launch_dq<E, D, NW>(p, a);
+    launch_dkdv2<E, D, NW>(p, a);
+  }
+}
+
+// All launches of one backward.
+template <class E, int D>
+void launch_bwd(const BwdPlan& p, const BwdArgs& a) {
+  if (p.mode != 1) {
+    launch_pre<E, D>(a);
+    p.mode == 0 ? launch_one_slice<E, D, 0>(a) : launch_one_slice<E, D, 2>(a);
+  } else if (D == 64 && p.nw == 2) {
+    launch_det<E, 64, 2>(p, a);
+  } else {
+    launch_det<E, D, 4>(p, a);
+  }
+  // folded already: no GQA | by the dK/dV kernel's last block per tile | by the dQ kernel
+  if (p.direct || p.fold != nullptr || p.fold3) return;
+  const long vec = (long)a.B * a.S * ((a.Hq + 2 * a.Hkv) * D / 4);
+  const int fin_blocks = (int)std::max(1L, std::min((vec + 255) / 256, 4096L));
+  hipLaunchKernelGGL((flash_bwd_finalize_kernel<E>), dim3(fin_blocks), dim3(256), 0, ft_stream(), a.dq_acc, a.dkp,
+                     a.dvp, a.dqkv, (long)a.B * a.S, a.Hq, a.Hkv, D, a.fold.cos_t, a.fold.sin_t, a.S,
+                     p.q_rot ? 1 : 0);
+}
+
 }  // namespace
+
+// rope.hip: in-place RoPE backward on the Q / K columns of dqkv
+void rope_bwd_(const at::Tensor& dqkv, const at::Tensor& cos_t, const at::Tensor& sin_t, int64_t seq_len,
+               int64_t hq, int64_t hkv, int64_t d);
+
+// flash_fwd, or -- doc_start given -- flash_doc_fwd: the document mask is built into the unsplit,
+// unpipelined kernel only.
+static std::tuple<at::Tensor, at::Tensor> run_fwd(const at::Tensor& qk, const at::Tensor& qkv,
+                                                  const at::Tensor* doc_start, int64_t S, int64_t Hq, int64_t Hkv,
+                                                  int64_t D) {
+  const int T = qk.size(0);
+  const int B = T / S;
+  const at::DeviceGuard guard(qk.device());
+  auto out = at::empty({T, Hq * D}, qk.options());
+  auto lse = at::empty({B, Hq, (long)stat_stride(S)}, qk.options().dtype(at::kFloat));
+  if (T == 0) return {out, lse};
+  const bool doc = doc_start != nullptr;
+  const int nqt = (S + 127) / 128;  // 4-wave blocks, see waves_per_block
+  const dim3 grid(nqt * B * Hq);
+  // key-split blocks when the grid is at most one block per CU (flash_set_fwd_split(0 / 1) forces)
+  const bool split = !doc && (g_fwd_split >= 0 ? g_fwd_split == 1 : (long)nqt * B * Hq <= 256);
+  const bool pipe = !doc && !split && g_fwd_pipe >= 1;
+  TORCH_CHECK(g_fwd_prof == nullptr || !pipe || (long)grid.x <= g_fwd_prof_rows,
+              "flash_set_fwd_prof: the buffer needs ", grid.x, " rows of 8 int64");
+  const FwdArgs a{cptr<bf16_t>(qk), cptr<bf16_t>(qkv), mptr<bf16_t>(out), mptr<float>(lse), B, (int)S, (int)Hq,
+                  (int)Hkv, LOG2E_F / std::sqrt((float)D), qk.size(-1), doc ? cptr<int>(*doc_start) : nullptr};
+  FT_DISPATCH_E16(qk.scalar_type(), {
+    if (D == 128) launch_fwd<E, 128>(a, grid, split, pipe); else launch_fwd<E, 64>(a, grid, split, pipe);
+  });
+  FT_LAUNCH_CHECK();
+  return {out, lse};
+}
+
+// flash_bwd, or -- doc_start / doc_end given -- flash_doc_bwd. cos_t / sin_t: null, or the checked
+// RoPE tables.
+static at::Tensor run_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv,
+                          const at::Tensor& out, const at::Tensor& lse, const at::Tensor* doc_start,
+                          const at::Tensor* doc_end, int64_t S, int64_t Hq, int64_t Hkv, int64_t D, int64_t mode,
+                          const at::Tensor* cos_t, const at::Tensor* sin_t) {
+  const int T = qk.size(0);
+  const int B = T / S;
+  const at::DeviceGuard guard(qk.device());
+  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
+  if (T == 0) return dqkv;
+  const bool rope = cos_t != nullptr;
+  const BwdPlan p = plan_bwd(qk.device(), S, B, Hq, Hkv, D, mode, rope, doc_start != nullptr);
+  auto f32 = qk.options().dtype(at::kFloat);
+  auto delta = at::empty({B, Hq, (long)stat_stride(S)}, f32);
+  at::Tensor dq_acc, dk_part, dv_part;
+  if (p.mode != 1) dq_acc = p.mode == 2 ? at::empty({T, Hq * D}, f32) : at::zeros({T, Hq * D}, f32);
+  if (!p.direct) {
+    dk_part = at::empty({T, Hq * D}, qk.options());
+    dv_part = at::empty({T, Hq * D}, qk.options());
+  }
+  bf16_t* const dq = mptr<bf16_t>(dqkv);
+  bf16_t* const dkp = p.direct ? dq + (long)Hq * D : mptr<bf16_t>(dk_part);
+  bf16_t* const dvp = p.direct ? dq + (long)(Hq + Hkv) * D : mptr<bf16_t>(dv_part);
+  const float* const cs = rope ? cptr<float>(*cos_t) : nullptr;
+  const float* const sn = rope ? cptr<float>(*sin_t) : nullptr;
+  const BwdArgs a{cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<bf16_t>(out), cptr<float>(lse),
+                  mptr<float>(delta), p.mode != 1 ? mptr<float>(dq_acc) : nullptr, dq, dkp, dvp,
+                  p.direct ? (long)(Hq + 2 * Hkv) * D : (long)Hq * D, B, (int)S, (int)Hq, (int)Hkv,
+                  LOG2E_F / std::sqrt((float)D), 1.f / std::sqrt((float)D), qk.size(-1),
+                  GqaFold{p.fold, dq, cs, sn, 0, p.q_rot ? 1 : 0, p.krot ? 1 : 0}, p.q_rot ? cs : nullptr,
+                  p.q_rot ? sn : nullptr, p.fold3 ? dkp : nullptr, p.fold3 ? dvp : nullptr,
+                  p.doc ? cptr<int>(*doc_start) : nullptr, p.doc ? cptr<int>(*doc_end) : nullptr};
+  FT_DISPATCH_E16(qk.scalar_type(), {
+    if (D == 128) launch_bwd<E, 128>(p, a); else launch_bwd<E, 64>(p, a);
+  });
+  FT_LAUNCH_CHECK();
+  // no GQA partials to fold: only the RoPE backward remains (unless done in-kernel)
+  if (p.direct && rope && !p.krot) rope_bwd_(dqkv, *cos_t, *sin_t, S, Hq, Hkv, D);
+  return dqkv;
+}
 
 // Returns (o [T, Hq*D] bf16, lse2 [B, Hq, Sp] fp32 with Sp = S rounded up to 32 (entries
 // >= S unused); lse2 = log2 of the softmax denominator in the exp2 domain, i.e.
@@ -1932,219 +2217,21 @@ void check_inputs(const at::Tensor& qk, const at::Tensor& qkv, int64_t S, int64_
 std::tuple<at::Tensor, at::Tensor> flash_fwd(const at::Tensor& qk, const at::Tensor& qkv,
                                              int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
   check_inputs(qk, qkv, S, Hq, Hkv, D);
-  const int T = qk.size(0);
-  const int B = T / S;
-  const at::DeviceGuard guard(qk.device());
-  auto out = at::empty({T, Hq * D}, qk.options());
-  auto lse = at::empty({B, Hq, (long)stat_stride(S)}, qk.options().dtype(at::kFloat));
-  const float sl2 = LOG2E_F / std::sqrt((float)D);
-  const long ldqk = qk.size(-1);
-  const int nw = 4;  // see waves_per_block
-  const int nqt = (S + 32 * nw - 1) / (32 * nw);
-  // key-split blocks when the grid is at most one block per CU (FT_FLASH_FWD_SPLIT=0/1 forces)
-  const bool split = g_fwd_split >= 0 ? g_fwd_split == 1 : (long)nqt * B * Hq <= 256;
-  dim3 grid(nqt * B * Hq), block(64 * nw * (split ? 2 : 1));
-#define FT_FWD(DD, SP)                                                                             \
-  hipLaunchKernelGGL((flash_fwd_kernel<E, DD, 4, SP>), grid, block, 0, ft_stream(), cptr<bf16_t>(qk), \
-                     cptr<bf16_t>(qkv), mptr<bf16_t>(out), mptr<float>(lse), B, (int)S, (int)Hq,   \
-                     (int)Hkv, sl2, ldqk)
-#define FT_FWD_PIPE(DD)                                                                            \
-  hipLaunchKernelGGL((flash_fwd_pipe_kernel<E, DD, 4>), grid, block, 0, ft_stream(), cptr<bf16_t>(qk), \
-                     cptr<bf16_t>(qkv), mptr<bf16_t>(out), mptr<float>(lse), B, (int)S, (int)Hq,   \
-                     (int)Hkv, sl2, ldqk, g_fwd_prof)
-  const bool pipe = !split && g_fwd_pipe >= 1;
-  TORCH_CHECK(g_fwd_prof == nullptr || !pipe || (long)grid.x <= g_fwd_prof_rows,
-              "flash_set_fwd_prof: the buffer needs ", grid.x, " rows of 8 int64");
-  FT_DISPATCH_E16(qk.scalar_type(), {
-    if (D == 128) {
-      if (split) FT_FWD(128, 2); else if (pipe) FT_FWD_PIPE(128); else FT_FWD(128, 1);
-    } else {
-      if (split) FT_FWD(64, 2); else if (pipe) FT_FWD_PIPE(64); else FT_FWD(64, 1);
-    }
-  });
-#undef FT_FWD
-#undef FT_FWD_PIPE
-  FT_LAUNCH_CHECK();
-  return {out, lse};
+  return run_fwd(qk, qkv, nullptr, S, Hq, Hkv, D);
 }
 
-// Returns dqkv [T, (Hq+2Hkv)*D] bf16 (dQ/dK in the rotated frame; RoPE backward follows).
-// rope.hip: in-place RoPE backward on the Q / K columns of dqkv
-void rope_bwd_(const at::Tensor& dqkv, const at::Tensor& cos_t, const at::Tensor& sin_t, int64_t seq_len,
-               int64_t hq, int64_t hkv, int64_t d);
-
-// cos / sin given: the returned dQ / dK are rotated back (the gradient of the UNROTATED
-// projection), inside the pass that folds the GQA dK / dV partials.
+// Returns dqkv [T, (Hq+2Hkv)*D] bf16: dQ / dK in the rotated frame, or -- cos / sin given --
+// rotated back (the gradient of the UNROTATED projection) inside the dQ kernel and the pass or
+// kernel that folds or stores dK. mode: see BwdPlan.
 at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv,
                      const at::Tensor& out, const at::Tensor& lse, int64_t S, int64_t Hq,
                      int64_t Hkv, int64_t D, int64_t mode, const std::optional<at::Tensor>& cos_t,
                      const std::optional<at::Tensor>& sin_t) {
   check_inputs(qk, qkv, S, Hq, Hkv, D);
-  FT_CHECK_CONTIG(dout);
-  FT_CHECK_CONTIG(out);
-  const int T = qk.size(0);
-  const int B = T / S;
-  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, "flash_bwd: o shape");
-  TORCH_CHECK(lse.numel() == (long)B * Hq * stat_stride(S), "flash_bwd: lse shape");
-  const at::DeviceGuard guard(qk.device());
-  auto f32 = qk.options().dtype(at::kFloat);
-  auto delta = at::empty({B, Hq, (long)stat_stride(S)}, f32);
-  // mode 0: dQ by fp32 atomics in the KV-major kernel (fastest);
-  // mode 1: deterministic — KV kernel without dQ + Q-major dQ kernel (no atomics);
-  // mode 2: timing experiment only (racy dQ stores).
-  const bool det = mode == 1;
-  at::Tensor dq_acc = det ? at::Tensor() : (mode == 2 ? at::empty({T, Hq * D}, f32) : at::zeros({T, Hq * D}, f32));
-  const int nw_ = waves_per_block(S, B, Hq, D);
-  // slice-pair dK/dV kernel in the deterministic mode (else the one-slice flash_bwd_kernel)
-  const bool use_dkdv2 = det && (D == 128 ? (g_dkdv2 && nw_ == 4) : (nw_ == 2 || g_dkdv2_64));
-  // no GQA: that kernel writes dK / dV into dqkv itself, dQ comes from the dQ kernel, so the
-  // finalize pass (and the partial buffers) are skipped
-  const bool direct = use_dkdv2 && Hq == Hkv;
-  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
-  at::Tensor dk_part = direct ? at::Tensor() : at::empty({T, Hq * D}, qk.options());
-  at::Tensor dv_part = direct ? at::Tensor() : at::empty({T, Hq * D}, qk.options());
-  bf16_t* dkp = direct ? mptr<bf16_t>(dqkv) + (long)Hq * D : mptr<bf16_t>(dk_part);
-  bf16_t* dvp = direct ? mptr<bf16_t>(dqkv) + (long)(Hq + Hkv) * D : mptr<bf16_t>(dv_part);
-  const long ldkv = direct ? (long)(Hq + 2 * Hkv) * D : (long)Hq * D;
-  const bool rope = cos_t.has_value() && cos_t->defined();
-  if (rope) {
-    TORCH_CHECK(sin_t.has_value() && sin_t->defined(), "flash_bwd: cos without sin");
-    FT_CHECK_F32((*cos_t));
-    FT_CHECK_F32((*sin_t));
-    FT_CHECK_CONTIG((*cos_t));
-    FT_CHECK_CONTIG((*sin_t));
-    TORCH_CHECK(cos_t->size(0) >= S && cos_t->size(1) == D / 2 && sin_t->sizes() == cos_t->sizes(),
-                "flash_bwd: rope tables must be [>= S, D / 2]");
-  }
-  const float sl2 = LOG2E_F / std::sqrt((float)D);
-  const float scale = 1.f / std::sqrt((float)D);
-  const long ldqk = qk.size(-1);
-  const long rows = (long)T * Hq;
-  // GQA fold inside the deterministic dK/dV kernel (no finalize launch): its tile counters
-  static const int fold_dbg = [] {
-    return 0;  // (1: no fold work, 2: no release fence -- the timing experiments of r4_flash_gqa_fold_probe)
-  }();
-  // RoPE backward of dQ in the dQ kernel's epilogue (deterministic mode, GQA partials to fold; the
-  // direct no-GQA path rotates Q and K in one rope_bwd_ pass)
-  // (no GQA: the dK rotation too happens in the dK/dV kernel's store, so no rope_bwd_ pass follows;
-  // flash_set_direct_rope(false) restores that pass, for A/B)
-  const bool krot = rope && direct && g_direct_rope;
-  const bool q_rot = rope && det && (!direct || krot);
-  const float* dq_cos = q_rot ? cptr<float>(*cos_t) : nullptr;
-  const float* dq_sin = q_rot ? cptr<float>(*sin_t) : nullptr;
-  GqaFold fold{nullptr, mptr<bf16_t>(dqkv), rope ? cptr<float>(*cos_t) : nullptr,
-               rope ? cptr<float>(*sin_t) : nullptr, fold_dbg, q_rot ? 1 : 0, krot ? 1 : 0};
-  // the in-kernel fold holds at most 8 q-head partials per unit (uint4 x[U][8]): wider groups
-  // take the finalize pass
-  if (use_dkdv2 && !direct && g_bwd_fold && Hq / Hkv <= 8)
-    fold.cnt = fold_counters(qk.device(), (long)B * Hkv * ((S + 32 * nw_ - 1) / (32 * nw_)));
-  // 3-kernel GQA backward (g_fold3): dK/dV first (delta from O), then dQ + the fold; a column slice
-  // of D / G columns per q-head block must be whole 16-B chunks
-  const bool fold3 = use_dkdv2 && !direct && g_fold3 && fold.cnt == nullptr && D % (8 * (Hq / Hkv)) == 0;
-  const bf16_t* fkp = fold3 ? dkp : nullptr;
-  const bf16_t* fvp = fold3 ? dvp : nullptr;
-  const int pre_blocks = (int)((rows * 16 + 255) / 256);
-  const int nkt = (S + 127) / 128;
-  dim3 grid(nkt * B * Hq), block(256);
-  const int nw = nw_;
-  const int nkt2 = (S + 32 * nw - 1) / (32 * nw);  // tiles of the deterministic dK/dV and dQ kernels
-  const dim3 grid2(nkt2 * B * Hq), block2(64 * nw);
-  float* dqp = det ? nullptr : mptr<float>(dq_acc);
-#define FT_BWD(DD, MODE)                                                                          \
-  hipLaunchKernelGGL((flash_bwd_kernel<E, DD, MODE>), grid, block, 0, ft_stream(), cptr<bf16_t>(dout), \
-                     cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse), cptr<float>(delta),     \
-                     dqp, dkp, dvp, B, (int)S, (int)Hq, (int)Hkv,                                    \
-                     sl2, scale, ldqk)
-  // dK/dV split, head_dim 64 only (at 128 the doubled block spills): FT_FLASH_KV_SPLIT=0/1
-  // forces; default: grids of at most one wave per SIMD
-  const bool kv_split = D == 64 && (g_kv_split >= 0 ? g_kv_split == 1 : (long)grid2.x * nw <= 1024);
-#define FT_DKDV2(DD, NW_, SP_)                                                                             \
-  if (fold3)                                                                                                 \
-    hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, DD, NW_, SP_, true>), grid2, dim3(64 * NW_ * SP_), 0,        \
-                       ft_stream(), cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse), \
-                       cptr<float>(delta), dkp, dvp, ldkv, B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk, fold, \
-                       cptr<bf16_t>(out));                                                                   \
-  else                                                                                                       \
-    hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, DD, NW_, SP_>), grid2, dim3(64 * NW_ * SP_), 0, ft_stream(), \
-                       cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse),         \
-                       cptr<float>(delta), dkp, dvp, ldkv, B, (int)S,                                     \
-                       (int)Hq, (int)Hkv, sl2, scale, ldqk, fold, nullptr)
-  // dQ key split by default (FT_FLASH_DQ_SPLIT=0 turns it off): S = 2048, 12 heads of 64:
-  // 94 -> 83 us for the whole backward; 8B layer 173 -> 167 us; S = 16384 1006 -> 972 us
-  // (profiles/r2_flash_key_split.log)
-  const bool dq_split = g_dq_split != 0;
-  // deterministic mode: the dQ kernel runs first and forms delta itself (no flash_bwd_pre pass),
-  // then the dK / dV kernel reads it
-#define FT_DQ(DD, NW_)                                                                                  \
-  if (dq_split)                                                                                         \
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<E, DD, NW_, 2>), grid2, dim3(128 * NW_), 0, ft_stream(),       \
-                       cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse),       \
-                       mptr<float>(delta), mptr<bf16_t>(dqkv), B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk, \
-                       cptr<bf16_t>(out), dq_cos, dq_sin, fkp, fvp);                                    \
-  else                                                                                                  \
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<E, DD, NW_, 1>), grid2, block2, 0, ft_stream(),                \
-                       cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse),       \
-                       mptr<float>(delta), mptr<bf16_t>(dqkv), B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk, \
-                       cptr<bf16_t>(out), dq_cos, dq_sin, fkp, fvp)
-  // the two deterministic kernels in their order: dQ first (it forms delta for the dK/dV kernel), or
-  // -- fold3 -- dK/dV first (forms delta itself) and dQ after it (folds the partials it wrote)
-#define FT_PAIR(DQ_STMT, KV_STMT) \
-  if (fold3) {                    \
-    KV_STMT;                      \
-    DQ_STMT;                      \
-  } else {                        \
-    DQ_STMT;                      \
-    KV_STMT;                      \
-  }
-#define FT_PRE(DD)                                                                                      \
-  hipLaunchKernelGGL((flash_bwd_pre_kernel<E, DD>), dim3(pre_blocks), block, 0, ft_stream(),             \
-                     cptr<bf16_t>(dout), cptr<bf16_t>(out), mptr<float>(delta), B, (int)S, (int)Hq)
-  FT_DISPATCH_E16(qk.scalar_type(), {
-    if (D == 128) {
-      if (mode == 0) { FT_PRE(128); FT_BWD(128, 0); }
-      else if (mode == 1) {
-        if (g_dkdv2 && nw == 4) { FT_PAIR({ FT_DQ(128, 4); }, { FT_DKDV2(128, 4, 1); }) }
-        else { FT_DQ(128, 4); FT_BWD(128, 1); }
-      }
-      else { FT_PRE(128); FT_BWD(128, 2); }
-    } else {
-      if (mode == 0) { FT_PRE(64); FT_BWD(64, 0); }
-      else if (mode == 1 && nw == 2) {
-        if (kv_split) { FT_PAIR({ FT_DQ(64, 2); }, { FT_DKDV2(64, 2, 2); }) }
-        else { FT_PAIR({ FT_DQ(64, 2); }, { FT_DKDV2(64, 2, 1); }) }
-      }
-      // head_dim 64 with 4-wave blocks: the one-slice dK/dV kernel is faster (S = 8192, 16 heads:
-      // 631 vs 783 us, profiles/r2_flash_long_context.log); FT_FLASH_DKDV2=2 forces the slice pair
-      else if (mode == 1) {
-        if (g_dkdv2_64 && kv_split) { FT_PAIR({ FT_DQ(64, 4); }, { FT_DKDV2(64, 4, 2); }) }
-        else if (g_dkdv2_64) { FT_PAIR({ FT_DQ(64, 4); }, { FT_DKDV2(64, 4, 1); }) }
-        else { FT_DQ(64, 4); FT_BWD(64, 1); }
-      }
-      else { FT_PRE(64); FT_BWD(64, 2); }
-    }
-  });
-#undef FT_BWD
-#undef FT_DKDV2
-#undef FT_DQ
-#undef FT_PAIR
-#undef FT_PRE
-  FT_LAUNCH_CHECK();
-  if (direct) {  // no GQA partials to fold: only the RoPE backward remains (unless done in-kernel)
-    if (rope && !krot) rope_bwd_(dqkv, *cos_t, *sin_t, S, Hq, Hkv, D);
-    return dqkv;
-  }
-  if (fold.cnt != nullptr) return dqkv;  // folded by the dK/dV kernel's last block per tile
-  if (fold3) return dqkv;                // folded by the dQ kernel
-  const long vec = (long)T * ((Hq + 2 * Hkv) * D / 4);
-  const int fin_blocks = (int)std::max(1L, std::min((vec + 255) / 256, 4096L));
-  FT_DISPATCH_E16(qk.scalar_type(),
-                  hipLaunchKernelGGL((flash_bwd_finalize_kernel<E>), dim3(fin_blocks), block, 0, ft_stream(),
-                                     det ? nullptr : cptr<float>(dq_acc), cptr<bf16_t>(dk_part),
-                                     cptr<bf16_t>(dv_part), mptr<bf16_t>(dqkv), (long)T, (int)Hq,
-                                     (int)Hkv, (int)D, rope ? cptr<float>(*cos_t) : nullptr,
-                                     rope ? cptr<float>(*sin_t) : nullptr, (int)S, q_rot ? 1 : 0));
-  FT_LAUNCH_CHECK();
-  return dqkv;
+  check_bwd("flash_bwd", dout, out, lse, qk, S, Hq, D);
+  const bool rope = check_rope("flash_bwd", cos_t, sin_t, S, D);
+  return run_bwd(dout, qk, qkv, out, lse, nullptr, nullptr, S, Hq, Hkv, D, mode, rope ? &*cos_t : nullptr,
+                 rope ? &*sin_t : nullptr);
 }
 
 // ================================================================== document-masked attention
@@ -2153,45 +2240,12 @@ at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Ten
 // token ids). Layouts, lse format and results are those of flash_fwd / flash_bwd(mode 1); with one
 // document per sequence (doc_start = 0, doc_end = S) they are bitwise those of the plain unsplit,
 // unpipelined kernels, which the DOC instantiations extend.
-namespace {
-
-void check_doc(const at::Tensor& qk, const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t S) {
-  const long B = qk.size(0) / S;
-  for (const at::Tensor* t : {&doc_start, &doc_end}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == qk.device(), "flash_doc: doc_start / doc_end must be on qk's device");
-    TORCH_CHECK(t->scalar_type() == at::kInt, "flash_doc: doc_start / doc_end must be int32");
-    TORCH_CHECK(t->is_contiguous(), "flash_doc: doc_start / doc_end must be contiguous");
-    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S, "flash_doc: doc_start / doc_end must be [B, S]");
-  }
-}
-
-}  // namespace
-
 std::tuple<at::Tensor, at::Tensor> flash_doc_fwd(const at::Tensor& qk, const at::Tensor& qkv,
                                                  const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t S,
                                                  int64_t Hq, int64_t Hkv, int64_t D) {
   check_inputs(qk, qkv, S, Hq, Hkv, D);
-  check_doc(qk, doc_start, doc_end, S);
-  const int T = qk.size(0);
-  const int B = T / S;
-  const at::DeviceGuard guard(qk.device());
-  auto out = at::empty({T, Hq * D}, qk.options());
-  auto lse = at::empty({B, Hq, (long)stat_stride(S)}, qk.options().dtype(at::kFloat));
-  if (T == 0) return {out, lse};
-  const float sl2 = LOG2E_F / std::sqrt((float)D);
-  const long ldqk = qk.size(-1);
-  const int nqt = (S + 127) / 128;
-  dim3 grid(nqt * B * Hq), block(256);
-#define FT_DOC_FWD(DD)                                                                                  \
-  hipLaunchKernelGGL((flash_fwd_kernel<E, DD, 4, 1, true>), grid, block, 0, ft_stream(), cptr<bf16_t>(qk), \
-                     cptr<bf16_t>(qkv), mptr<bf16_t>(out), mptr<float>(lse), B, (int)S, (int)Hq, (int)Hkv, \
-                     sl2, ldqk, cptr<int>(doc_start))
-  FT_DISPATCH_E16(qk.scalar_type(), {
-    if (D == 128) FT_DOC_FWD(128); else FT_DOC_FWD(64);
-  });
-#undef FT_DOC_FWD
-  FT_LAUNCH_CHECK();
-  return {out, lse};
+  ft_check_doc_bounds("flash_doc", qk, doc_start, doc_end, S);
+  return run_fwd(qk, qkv, &doc_start, S, Hq, Hkv, D);
 }
 
 // The deterministic backward (flash_bwd mode 1) with the document mask: the unsplit dQ kernel (it
@@ -2202,82 +2256,11 @@ at::Tensor flash_doc_bwd(const at::Tensor& dout, const at::Tensor& qk, const at:
                          const at::Tensor& doc_end, int64_t S, int64_t Hq, int64_t Hkv, int64_t D,
                          const std::optional<at::Tensor>& cos_t, const std::optional<at::Tensor>& sin_t) {
   check_inputs(qk, qkv, S, Hq, Hkv, D);
-  check_doc(qk, doc_start, doc_end, S);
-  FT_CHECK_CONTIG(dout);
-  FT_CHECK_CONTIG(out);
-  TORCH_CHECK(dout.scalar_type() == qk.scalar_type() && out.scalar_type() == qk.scalar_type(),
-              "flash_doc_bwd: dout / out dtype");
-  const int T = qk.size(0);
-  const int B = T / S;
-  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, "flash_doc_bwd: o shape");
-  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.numel() == (long)B * Hq * stat_stride(S),
-              "flash_doc_bwd: lse shape");
-  const at::DeviceGuard guard(qk.device());
-  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
-  if (T == 0) return dqkv;
-  auto delta = at::empty({B, Hq, (long)stat_stride(S)}, qk.options().dtype(at::kFloat));
-  const int nw = waves_per_block(S, B, Hq, D);
-  const bool direct = Hq == Hkv;  // no GQA: dK / dV straight into dqkv
-  at::Tensor dk_part = direct ? at::Tensor() : at::empty({T, Hq * D}, qk.options());
-  at::Tensor dv_part = direct ? at::Tensor() : at::empty({T, Hq * D}, qk.options());
-  bf16_t* dkp = direct ? mptr<bf16_t>(dqkv) + (long)Hq * D : mptr<bf16_t>(dk_part);
-  bf16_t* dvp = direct ? mptr<bf16_t>(dqkv) + (long)(Hq + Hkv) * D : mptr<bf16_t>(dv_part);
-  const long ldkv = direct ? (long)(Hq + 2 * Hkv) * D : (long)Hq * D;
-  const bool rope = cos_t.has_value() && cos_t->defined();
-  if (rope) {
-    TORCH_CHECK(sin_t.has_value() && sin_t->defined(), "flash_doc_bwd: cos without sin");
-    FT_CHECK_F32((*cos_t));
-    FT_CHECK_F32((*sin_t));
-    FT_CHECK_CONTIG((*cos_t));
-    FT_CHECK_CONTIG((*sin_t));
-    TORCH_CHECK(cos_t->size(0) >= S && cos_t->size(1) == D / 2 && sin_t->sizes() == cos_t->sizes(),
-                "flash_doc_bwd: rope tables must be [>= S, D / 2]");
-  }
-  const float sl2 = LOG2E_F / std::sqrt((float)D);
-  const float scale = 1.f / std::sqrt((float)D);
-  const long ldqk = qk.size(-1);
-  // the RoPE backward as in flash_bwd(mode 1): dQ in the dQ kernel's store; dK in the finalize pass
-  // (GQA) or in the dK/dV kernel's store (no GQA; flash_set_direct_rope(false): a rope_bwd_ pass)
-  const bool krot = rope && direct && g_direct_rope;
-  const bool q_rot = rope && (!direct || krot);
-  const float* dq_cos = q_rot ? cptr<float>(*cos_t) : nullptr;
-  const float* dq_sin = q_rot ? cptr<float>(*sin_t) : nullptr;
-  GqaFold fold{nullptr, mptr<bf16_t>(dqkv), rope ? cptr<float>(*cos_t) : nullptr,
-               rope ? cptr<float>(*sin_t) : nullptr, 0, q_rot ? 1 : 0, krot ? 1 : 0};
-  const dim3 grid((unsigned)(((S + 32 * nw - 1) / (32 * nw)) * B * Hq)), block(64 * nw);
-#define FT_DOC_BWD(DD, NW_)                                                                                  \
-  hipLaunchKernelGGL((flash_bwd_dq_kernel<E, DD, NW_, 1, true>), grid, block, 0, ft_stream(), cptr<bf16_t>(dout), \
-                     cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse), mptr<float>(delta),              \
-                     mptr<bf16_t>(dqkv), B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk, cptr<bf16_t>(out),  \
-                     dq_cos, dq_sin, nullptr, nullptr, cptr<int>(doc_start));                                \
-  hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, DD, NW_, 1, false, true>), grid, block, 0, ft_stream(),      \
-                     cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<float>(lse),              \
-                     cptr<float>(delta), dkp, dvp, ldkv, B, (int)S, (int)Hq, (int)Hkv, sl2, scale, ldqk,     \
-                     fold, nullptr, cptr<int>(doc_end))
-  FT_DISPATCH_E16(qk.scalar_type(), {
-    if (D == 128) {
-      FT_DOC_BWD(128, 4);
-    } else if (nw == 2) {
-      FT_DOC_BWD(64, 2);
-    } else {
-      FT_DOC_BWD(64, 4);
-    }
-  });
-#undef FT_DOC_BWD
-  FT_LAUNCH_CHECK();
-  if (direct) {
-    if (rope && !krot) rope_bwd_(dqkv, *cos_t, *sin_t, S, Hq, Hkv, D);
-    return dqkv;
-  }
-  const long vec = (long)T * ((Hq + 2 * Hkv) * D / 4);
-  const int fin_blocks = (int)std::max(1L, std::min((vec + 255) / 256, 4096L));
-  FT_DISPATCH_E16(qk.scalar_type(),
-                  hipLaunchKernelGGL((flash_bwd_finalize_kernel<E>), dim3(fin_blocks), dim3(256), 0, ft_stream(),
-                                     nullptr, cptr<bf16_t>(dk_part), cptr<bf16_t>(dv_part), mptr<bf16_t>(dqkv),
-                                     (long)T, (int)Hq, (int)Hkv, (int)D, rope ? cptr<float>(*cos_t) : nullptr,
-                                     rope ? cptr<float>(*sin_t) : nullptr, (int)S, q_rot ? 1 : 0));
-  FT_LAUNCH_CHECK();
-  return dqkv;
+  ft_check_doc_bounds("flash_doc", qk, doc_start, doc_end, S);
+  check_bwd("flash_doc_bwd", dout, out, lse, qk, S, Hq, D);
+  const bool rope = check_rope("flash_doc_bwd", cos_t, sin_t, S, D);
+  return run_bwd(dout, qk, qkv, out, lse, &doc_start, &doc_end, S, Hq, Hkv, D, 1, rope ? &*cos_t : nullptr,
+                 rope ? &*sin_t : nullptr);
 }
 
 // Same-process A/B switch: slice-pair dK/dV kernel vs flash_bwd_kernel<D, 1>.
@@ -2326,3 +2309,4 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
       "int S, int Hq, int Hkv, int D, Tensor? cos=None, Tensor? sin=None) -> Tensor",
       &flash_doc_bwd);
 }
+

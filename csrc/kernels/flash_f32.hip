@@ -308,15 +308,79 @@ void check_f32(const at::Tensor& qk, const at::Tensor& qkv, int64_t S, int64_t H
   TORCH_CHECK(qk.size(0) == qkv.size(0) && qk.size(0) % S == 0, "flash_f32: rows");
 }
 
-void check_f32_doc(const at::Tensor& qk, const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t S) {
-  const long B = qk.size(0) / S;
-  for (const at::Tensor* t : {&doc_start, &doc_end}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == qk.device(), "flash_f32_doc: doc_start / doc_end must be on qk's device");
-    TORCH_CHECK(t->scalar_type() == at::kInt, "flash_f32_doc: doc_start / doc_end must be int32");
-    TORCH_CHECK(t->is_contiguous(), "flash_f32_doc: doc_start / doc_end must be contiguous");
-    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S,
-                "flash_f32_doc: doc_start / doc_end must be [B, S]");
+template <int D, bool DOC>
+void launch_f32_fwd(const at::Tensor& qk, const at::Tensor& qkv, const at::Tensor& out, const at::Tensor& lse,
+                    int B, int S, int Hq, int Hkv, const int* doc_start) {
+  hipLaunchKernelGGL((attn_f32_fwd_kernel<D, DOC>), dim3(((S + TR - 1) / TR) * B * Hq), dim3(NT), 0, ft_stream(),
+                     cptr<float>(qk), cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, S, Hq, Hkv,
+                     1.f / std::sqrt((float)D), (long)qk.size(-1), doc_start);
+}
+
+// flash_f32_fwd, or -- doc_start given -- flash_f32_doc_fwd
+std::tuple<at::Tensor, at::Tensor> f32_fwd(const at::Tensor& qk, const at::Tensor& qkv, const at::Tensor* doc_start,
+                                           int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
+  const int T = qk.size(0), B = T / S;
+  const at::DeviceGuard guard(qk.device());
+  auto out = at::empty({T, Hq * D}, qk.options());
+  auto lse = at::empty({B, Hq, S}, qk.options());
+  if (T == 0) return {out, lse};
+  if (doc_start != nullptr) {
+    const int* ds = cptr<int>(*doc_start);
+    if (D == 128) launch_f32_fwd<128, true>(qk, qkv, out, lse, B, S, Hq, Hkv, ds);
+    else launch_f32_fwd<64, true>(qk, qkv, out, lse, B, S, Hq, Hkv, ds);
+  } else {
+    if (D == 128) launch_f32_fwd<128, false>(qk, qkv, out, lse, B, S, Hq, Hkv, nullptr);
+    else launch_f32_fwd<64, false>(qk, qkv, out, lse, B, S, Hq, Hkv, nullptr);
   }
+  FT_LAUNCH_CHECK();
+  return {out, lse};
+}
+
+// delta, then dQ (query-major) and dK / dV (key-major, the GQA group in head order)
+template <int D, bool DOC>
+void launch_f32_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv, const at::Tensor& out,
+                    const at::Tensor& lse, const at::Tensor& delta, const at::Tensor& dqkv, int B, int S, int Hq,
+                    int Hkv, const int* doc_start, const int* doc_end) {
+  const float scale = 1.f / std::sqrt((float)D);
+  const long ldqk = qk.size(-1);
+  const int nt = (S + TR - 1) / TR;
+  const int pre = (int)(((long)B * S * Hq * 4 + NT - 1) / NT);
+  hipLaunchKernelGGL(attn_f32_delta_kernel<D>, dim3(pre), dim3(NT), 0, ft_stream(), cptr<float>(dout),
+                     cptr<float>(out), mptr<float>(delta), B, S, Hq);
+  hipLaunchKernelGGL((attn_f32_dq_kernel<D, DOC>), dim3(nt * B * Hq), dim3(NT), 0, ft_stream(), cptr<float>(dout),
+                     cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse), cptr<float>(delta), mptr<float>(dqkv), B, S,
+                     Hq, Hkv, scale, ldqk, doc_start);
+  hipLaunchKernelGGL((attn_f32_dkdv_kernel<D, DOC>), dim3(nt * B * Hkv), dim3(NT), 0, ft_stream(), cptr<float>(dout),
+                     cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse), cptr<float>(delta), mptr<float>(dqkv), B, S,
+                     Hq, Hkv, scale, ldqk, doc_start, doc_end);
+}
+
+// flash_f32_bwd, or -- doc_start / doc_end given -- flash_f32_doc_bwd (`op`: the message prefix)
+at::Tensor f32_bwd(const char* op, const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv,
+                   const at::Tensor& out, const at::Tensor& lse, const at::Tensor* doc_start,
+                   const at::Tensor* doc_end, int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
+  FT_CHECK_F32(dout);
+  FT_CHECK_F32(out);
+  FT_CHECK_F32(lse);
+  FT_CHECK_CONTIG(dout);
+  FT_CHECK_CONTIG(out);
+  const int T = qk.size(0), B = T / S;
+  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, op, ": o shape");
+  TORCH_CHECK(lse.numel() == (long)B * Hq * S, op, ": lse shape");
+  const at::DeviceGuard guard(qk.device());
+  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
+  if (T == 0) return dqkv;
+  auto delta = at::empty({B, Hq, S}, qk.options());
+  if (doc_start != nullptr) {
+    const int *ds = cptr<int>(*doc_start), *de = cptr<int>(*doc_end);
+    if (D == 128) launch_f32_bwd<128, true>(dout, qk, qkv, out, lse, delta, dqkv, B, S, Hq, Hkv, ds, de);
+    else launch_f32_bwd<64, true>(dout, qk, qkv, out, lse, delta, dqkv, B, S, Hq, Hkv, ds, de);
+  } else {
+    if (D == 128) launch_f32_bwd<128, false>(dout, qk, qkv, out, lse, delta, dqkv, B, S, Hq, Hkv, nullptr, nullptr);
+    else launch_f32_bwd<64, false>(dout, qk, qkv, out, lse, delta, dqkv, B, S, Hq, Hkv, nullptr, nullptr);
+  }
+  FT_LAUNCH_CHECK();
+  return dqkv;
 }
 
 }  // namespace
@@ -325,24 +389,7 @@ void check_f32_doc(const at::Tensor& qk, const at::Tensor& doc_start, const at::
 std::tuple<at::Tensor, at::Tensor> flash_f32_fwd(const at::Tensor& qk, const at::Tensor& qkv,
                                                  int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
   check_f32(qk, qkv, S, Hq, Hkv, D);
-  const int T = qk.size(0), B = T / S;
-  const at::DeviceGuard guard(qk.device());
-  auto out = at::empty({T, Hq * D}, qk.options());
-  auto lse = at::empty({B, Hq, S}, qk.options());
-  const float scale = 1.f / std::sqrt((float)D);
-  const dim3 grid(((S + TR - 1) / TR) * B * Hq);
-  if (T > 0) {
-    if (D == 128)
-      hipLaunchKernelGGL(attn_f32_fwd_kernel<128>, grid, dim3(NT), 0, ft_stream(), cptr<float>(qk),
-                         cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, (int)S, (int)Hq,
-                         (int)Hkv, scale, (long)qk.size(-1));
-    else
-      hipLaunchKernelGGL(attn_f32_fwd_kernel<64>, grid, dim3(NT), 0, ft_stream(), cptr<float>(qk),
-                         cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, (int)S, (int)Hq,
-                         (int)Hkv, scale, (long)qk.size(-1));
-    FT_LAUNCH_CHECK();
-  }
-  return {out, lse};
+  return f32_fwd(qk, qkv, nullptr, S, Hq, Hkv, D);
 }
 
 // Returns dqkv [T, (Hq+2Hkv)*D] fp32 (dQ / dK in the frame of qk, as flash_bwd).
@@ -350,38 +397,7 @@ at::Tensor flash_f32_bwd(const at::Tensor& dout, const at::Tensor& qk, const at:
                          const at::Tensor& out, const at::Tensor& lse, int64_t S, int64_t Hq,
                          int64_t Hkv, int64_t D) {
   check_f32(qk, qkv, S, Hq, Hkv, D);
-  FT_CHECK_F32(dout);
-  FT_CHECK_F32(out);
-  FT_CHECK_CONTIG(dout);
-  FT_CHECK_CONTIG(out);
-  const int T = qk.size(0), B = T / S;
-  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, "flash_f32_bwd: o shape");
-  TORCH_CHECK(lse.numel() == (long)B * Hq * S, "flash_f32_bwd: lse shape");
-  const at::DeviceGuard guard(qk.device());
-  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
-  if (T == 0) return dqkv;
-  auto delta = at::empty({B, Hq, S}, qk.options());
-  const float scale = 1.f / std::sqrt((float)D);
-  const long ldqk = qk.size(-1);
-  const int nt = (S + TR - 1) / TR;
-  const int pre = (int)(((long)T * Hq * 4 + NT - 1) / NT);
-#define FT_F32_BWD(DD)                                                                              \
-  hipLaunchKernelGGL(attn_f32_delta_kernel<DD>, dim3(pre), dim3(NT), 0, ft_stream(), cptr<float>(dout), \
-                     cptr<float>(out), mptr<float>(delta), B, (int)S, (int)Hq);                      \
-  hipLaunchKernelGGL(attn_f32_dq_kernel<DD>, dim3(nt * B * Hq), dim3(NT), 0, ft_stream(),            \
-                     cptr<float>(dout), cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse),         \
-                     cptr<float>(delta), mptr<float>(dqkv), B, (int)S, (int)Hq, (int)Hkv, scale, ldqk); \
-  hipLaunchKernelGGL(attn_f32_dkdv_kernel<DD>, dim3(nt * B * Hkv), dim3(NT), 0, ft_stream(),         \
-                     cptr<float>(dout), cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse),         \
-                     cptr<float>(delta), mptr<float>(dqkv), B, (int)S, (int)Hq, (int)Hkv, scale, ldqk)
-  if (D == 128) {
-    FT_F32_BWD(128);
-  } else {
-    FT_F32_BWD(64);
-  }
-#undef FT_F32_BWD
-  FT_LAUNCH_CHECK();
-  return dqkv;
+  return f32_bwd("flash_f32_bwd", dout, qk, qkv, out, lse, nullptr, nullptr, S, Hq, Hkv, D);
 }
 
 // flash_f32_fwd / flash_f32_bwd with the document mask (see attn_f32_fwd_kernel).
@@ -389,67 +405,16 @@ std::tuple<at::Tensor, at::Tensor> flash_f32_doc_fwd(const at::Tensor& qk, const
                                                      const at::Tensor& doc_start, const at::Tensor& doc_end,
                                                      int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
   check_f32(qk, qkv, S, Hq, Hkv, D);
-  check_f32_doc(qk, doc_start, doc_end, S);
-  const int T = qk.size(0), B = T / S;
-  const at::DeviceGuard guard(qk.device());
-  auto out = at::empty({T, Hq * D}, qk.options());
-  auto lse = at::empty({B, Hq, S}, qk.options());
-  const float scale = 1.f / std::sqrt((float)D);
-  const dim3 grid(((S + TR - 1) / TR) * B * Hq);
-  if (T > 0) {
-    if (D == 128)
-      hipLaunchKernelGGL((attn_f32_fwd_kernel<128, true>), grid, dim3(NT), 0, ft_stream(), cptr<float>(qk),
-                         cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, (int)S, (int)Hq,
-                         (int)Hkv, scale, (long)qk.size(-1), cptr<int>(doc_start));
-    else
-      hipLaunchKernelGGL((attn_f32_fwd_kernel<64, true>), grid, dim3(NT), 0, ft_stream(), cptr<float>(qk),
-                         cptr<float>(qkv), mptr<float>(out), mptr<float>(lse), B, (int)S, (int)Hq,
-                         (int)Hkv, scale, (long)qk.size(-1), cptr<int>(doc_start));
-    FT_LAUNCH_CHECK();
-  }
-  return {out, lse};
+  ft_check_doc_bounds("flash_f32_doc", qk, doc_start, doc_end, S);
+  return f32_fwd(qk, qkv, &doc_start, S, Hq, Hkv, D);
 }
 
 at::Tensor flash_f32_doc_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Tensor& qkv,
                              const at::Tensor& out, const at::Tensor& lse, const at::Tensor& doc_start,
                              const at::Tensor& doc_end, int64_t S, int64_t Hq, int64_t Hkv, int64_t D) {
   check_f32(qk, qkv, S, Hq, Hkv, D);
-  check_f32_doc(qk, doc_start, doc_end, S);
-  FT_CHECK_F32(dout);
-  FT_CHECK_F32(out);
-  FT_CHECK_F32(lse);
-  FT_CHECK_CONTIG(dout);
-  FT_CHECK_CONTIG(out);
-  const int T = qk.size(0), B = T / S;
-  TORCH_CHECK(dout.numel() == (long)T * Hq * D && out.numel() == (long)T * Hq * D, "flash_f32_doc_bwd: o shape");
-  TORCH_CHECK(lse.numel() == (long)B * Hq * S, "flash_f32_doc_bwd: lse shape");
-  const at::DeviceGuard guard(qk.device());
-  auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
-  if (T == 0) return dqkv;
-  auto delta = at::empty({B, Hq, S}, qk.options());
-  const float scale = 1.f / std::sqrt((float)D);
-  const long ldqk = qk.size(-1);
-  const int nt = (S + TR - 1) / TR;
-  const int pre = (int)(((long)T * Hq * 4 + NT - 1) / NT);
-#define FT_F32_DOC_BWD(DD)                                                                           \
-  hipLaunchKernelGGL(attn_f32_delta_kernel<DD>, dim3(pre), dim3(NT), 0, ft_stream(), cptr<float>(dout), \
-                     cptr<float>(out), mptr<float>(delta), B, (int)S, (int)Hq);                      \
-  hipLaunchKernelGGL((attn_f32_dq_kernel<DD, true>), dim3(nt * B * Hq), dim3(NT), 0, ft_stream(),    \
-                     cptr<float>(dout), cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse),         \
-                     cptr<float>(delta), mptr<float>(dqkv), B, (int)S, (int)Hq, (int)Hkv, scale, ldqk, \
-                     cptr<int>(doc_start));                                                          \
-  hipLaunchKernelGGL((attn_f32_dkdv_kernel<DD, true>), dim3(nt * B * Hkv), dim3(NT), 0, ft_stream(), \
-                     cptr<float>(dout), cptr<float>(qk), cptr<float>(qkv), cptr<float>(lse),         \
-                     cptr<float>(delta), mptr<float>(dqkv), B, (int)S, (int)Hq, (int)Hkv, scale, ldqk, \
-                     cptr<int>(doc_start), cptr<int>(doc_end))
-  if (D == 128) {
-    FT_F32_DOC_BWD(128);
-  } else {
-    FT_F32_DOC_BWD(64);
-  }
-#undef FT_F32_DOC_BWD
-  FT_LAUNCH_CHECK();
-  return dqkv;
+  ft_check_doc_bounds("flash_f32_doc", qk, doc_start, doc_end, S);
+  return f32_bwd("flash_f32_doc_bwd", dout, qk, qkv, out, lse, &doc_start, &doc_end, S, Hq, Hkv, D);
 }
 
 TORCH_LIBRARY_FRAGMENT(ftamd, m) {
@@ -468,3 +433,4 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
       "int Hkv, int D) -> Tensor",
       &flash_f32_bwd);
 }
+

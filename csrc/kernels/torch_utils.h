@@ -71,6 +71,19 @@ static inline hipStream_t ft_stream() {
     }                                            \
   } while (0)
 
+// doc_start / doc_end of the document-masked attention ops: int32 [B, S] on qk's device
+// (`op`: the message prefix).
+static inline void ft_check_doc_bounds(const char* op, const at::Tensor& qk, const at::Tensor& doc_start,
+                                       const at::Tensor& doc_end, int64_t S) {
+  const long B = qk.size(0) / S;
+  for (const at::Tensor* t : {&doc_start, &doc_end}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qk.device(), op, ": doc_start / doc_end must be on qk's device");
+    TORCH_CHECK(t->scalar_type() == at::kInt, op, ": doc_start / doc_end must be int32");
+    TORCH_CHECK(t->is_contiguous(), op, ": doc_start / doc_end must be contiguous");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == B && t->size(1) == S, op, ": doc_start / doc_end must be [B, S]");
+  }
+}
+
 template <typename T>
 static inline const T* cptr(const at::Tensor& t) {
   return reinterpret_cast<const T*>(t.data_ptr());

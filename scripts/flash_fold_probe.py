@@ -1,7 +1,10 @@
 """Times the deterministic flash backward at the 8B layer shape with the GQA fold in the dK/dV kernel
-vs the finalize pass (and, via FT_FLASH_FOLD_DBG, the fold's parts).
+vs the finalize pass.
 
-    FT_FLASH_FOLD_DBG=0|1|2 python scripts/flash_fold_probe.py
+    python scripts/flash_fold_probe.py
+
+(FT_FLASH_FOLD_DBG, which profiles/r4_flash_gqa_fold_probe.log used to time the fold's parts, is no
+longer read by the kernel library: the "dbg" column below always shows the full fold.)
 """
 import os
 import sys

@@ -26,6 +26,9 @@ def rel(a, b):
     "B,S,Hq,Hkv,D",
     [(1, 128, 2, 1, 128), (1, 256, 4, 2, 128), (2, 192, 4, 4, 64), (1, 2048, 32, 8, 128), (1, 320, 8, 2, 64),
      (2, 512, 12, 12, 64),
+     # head_dim 64 with 4-wave blocks (4 tiles x 8 x 16 = 512 blocks, the smallest grid that selects them):
+     # mode 1 = the 4-wave dQ kernel + the one-slice dK/dV kernel
+     (8, 512, 16, 4, 64),
      # long context (reduced heads) and sequence lengths that are not multiples of the 32/64/128 tiles
      (1, 8192, 4, 1, 128), (1, 1000, 4, 2, 128), (2, 2047, 2, 1, 64), (1, 33, 2, 2, 128), (3, 100, 4, 4, 64)],
 )
@@ -225,7 +228,8 @@ def test_flash_dkdv_split_matches(B, S, Hq, Hkv, D):
 
 @pytest.mark.parametrize("B,S,Hq,Hkv,D,mode", [(1, 2048, 32, 8, 128, 1), (1, 512, 8, 2, 64, 1), (2, 256, 4, 4, 64, 1),
                                               (1, 1000, 4, 2, 128, 0), (2, 512, 12, 12, 64, 1),
-                                              (1, 1024, 8, 8, 128, 1), (1, 300, 16, 16, 64, 1)])
+                                              (1, 1024, 8, 8, 128, 1), (1, 300, 16, 16, 64, 1),
+                                              (8, 512, 16, 4, 64, 1)])  # head_dim 64, 4-wave blocks
 def test_flash_bwd_with_rope_backward(B, S, Hq, Hkv, D, mode):
     """flash_bwd(..., cos, sin): the gradient of the UNROTATED projection, the RoPE backward done
     in the pass that folds the GQA partials, or -- no GQA -- in the dQ and dK/dV kernels' stores
