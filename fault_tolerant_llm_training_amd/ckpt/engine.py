@@ -31,6 +31,13 @@ record (zlib ``crc32_combine``) and writes the headers/central directory, then
 renames. No rank ever holds the full optimizer state and D2H/disk bandwidth
 scale with W.
 
+Every file carries a ``state_digest`` record (:mod:`.verify`): the exact position-weighted
+digest of each flat buffer, formed by the ``digest_accum_`` kernel on the snapshot stream (over
+the HBM staging copy behind the snapshot event in ``hbm`` mode, so neither :meth:`fence` nor the
+next optimizer step waits for it) and copied into a small pinned block ahead of the drain event.
+The writer reads that block like any other buffer once the drain is done: no host sync, no pass
+over host memory. A resume checks the restored buffers against it.
+
 CPU tensors (tests, ``--device cpu``) take the same path with a synchronous
 host copy. Without the native runtime the writer falls back to ``torch.save``
 (temp file + fsync + rename) on a Python thread.
@@ -41,6 +48,7 @@ import os
 import tempfile
 import threading
 import time
+import zlib
 from dataclasses import dataclass, field
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
@@ -50,6 +58,8 @@ import torch
 
 from .._native import runtime, runtime_available
 from .format import ARCHIVE, archive_records, write_archive_python
+from .verify import RECORD_NAME, DigestEntry, dtype_name, pack_record, record_size, value_offset
+from ..utils.digest import MASK64, _KERNEL_DTYPES, digest_accum, digest_int
 
 
 @dataclass
@@ -121,10 +131,10 @@ class _InFlight:
 class CheckpointEngine:
     def __init__(self, buffers, mode: str = "auto", writer_threads: int = 8,
                  fsync: bool = True, hbm_headroom_gb: float = 16.0, group=None, rank: int = 0, world: int = 1,
-                 sharded: Optional[bool] = None):
+                 sharded: Optional[bool] = None, digest: bool = True):
         """``buffers``: name → flat device (or CPU) tensor holding training state (single
         writer), or a list of :class:`Region` (this rank's pieces; ``world`` > 1 → sharded
-        save over the gloo ``group``)."""
+        save over the gloo ``group``). ``digest``: put a ``state_digest`` record into every file."""
         if isinstance(buffers, dict):
             self.regions = [Region.whole(k, v) for k, v in buffers.items()]
         else:
@@ -149,6 +159,14 @@ class CheckpointEngine:
         self._host: Optional[Dict[str, torch.Tensor]] = None
         self._stage: Optional[Dict[str, torch.Tensor]] = None
         self._eng = None
+        # state digests: device kernel for GPU buffers (bf16 / fp16 / fp32), the PyTorch composition
+        # for CPU buffers; none without the native writer (torch.save fallback)
+        self.digest = bool(digest) and self.native and (
+            not self.is_cuda or all(b.dtype in _KERNEL_DTYPES for b in self.buffers.values()))
+        self._dg_acc: Optional[torch.Tensor] = None    # int64[len(regions)] on the device
+        self._dg_host: Optional[torch.Tensor] = None   # pinned: the record (single writer) / the values (sharded)
+        self._dg_cpu: Optional[List[int]] = None       # CPU engine: this rank's digests of the last snapshot
+        self._dg_stream = None
         self._snap_ev: Optional[int] = None
         self._inflight: Optional[_InFlight] = None
         self.history: List[SaveStats] = []
@@ -225,12 +243,28 @@ class CheckpointEngine:
         return self._ensure_host()
 
     # ------------------------------------------------------------------ snapshot
+    def _dg_slot(self, i: int) -> int:
+        """Byte offset of region ``i``'s digest in the pinned block."""
+        return 8 * i if self.sharded else value_offset(i)
+
+    def _enqueue_digests(self, src: Dict[str, torch.Tensor]) -> None:
+        """On the snapshot stream: zero the accumulator, then one streaming pass per piece."""
+        with torch.cuda.stream(self._dg_stream):
+            self._dg_acc.zero_()
+            for i, r in enumerate(self.regions):
+                t = src[r.name]
+                for flat_lo, data_off, n in r.pieces:
+                    digest_accum(self._dg_acc, i, t[data_off : data_off + n], flat_lo)
+
     def _snapshot(self) -> Optional[int]:
         """Enqueue the copies; returns the native event index the writer must wait on."""
         host = self._ensure_host()
         if not self.is_cuda:
             for k, b in self.buffers.items():
                 host[k].copy_(b)
+            if self.digest:
+                self._dg_cpu = [sum(digest_int(host[r.name][off : off + n], lo) for lo, off, n in r.pieces) & MASK64
+                                for r in self.regions]
             return None
         if not self.native:
             # no native engine: synchronous pinned copies on the current stream
@@ -242,6 +276,12 @@ class CheckpointEngine:
         if self._eng is None:
             self._eng = rt.SnapshotEngine(self.device.index or 0)
         eng = self._eng
+        if self.digest and self._dg_acc is None:
+            nreg = len(self.regions)
+            self._dg_acc = torch.zeros(nreg, dtype=torch.int64, device=self.device)
+            self._dg_host = rt.pinned_empty(8 * nreg if self.sharded else record_size(nreg), self.device.index or 0)
+            self._dg_host.zero_()
+            self._dg_stream = torch.cuda.ExternalStream(eng.stream_handle(), device=self.device)
         eng.begin(torch.cuda.current_stream(self.device).cuda_stream)
         if self.mode == "hbm":
             stage = self._ensure_stage()
@@ -251,8 +291,13 @@ class CheckpointEngine:
             src = stage
         else:
             src = self.buffers
+        if self.digest:
+            self._enqueue_digests(src)
         for k, b in src.items():
             eng.copy(host[k].data_ptr(), b.data_ptr(), b.numel() * b.element_size())
+        if self.digest:
+            for i in range(len(self.regions)):
+                eng.copy(self._dg_host.data_ptr() + self._dg_slot(i), self._dg_acc.data_ptr() + 8 * i, 8)
         drained = eng.mark()
         if self.mode != "hbm":
             self._snap_ev = drained
@@ -295,6 +340,8 @@ class CheckpointEngine:
                 inf.keep.append(storage)
             for name, data in small[4:]:
                 w.add_bytes(name, data)
+            if self.digest:
+                self._add_digest_record(w, storages, inf)
             handle = self._eng.event_handle(ev) if (ev is not None and self._eng is not None) else 0
             w.start(handle, self.fsync)
             inf.writer = w
@@ -319,6 +366,33 @@ class CheckpointEngine:
             self.wait()
         st.stall_s = time.perf_counter() - t0 if blocking else st.snapshot_s
         return st
+
+    def _digest_entries(self, storages, values: Optional[List[int]]) -> List[DigestEntry]:
+        """One entry per region; ``record`` is the archive member whose storage is the region's
+        host copy (or placeholder), matched by storage pointer."""
+        by_ptr = {st.data_ptr(): f"data/{key}" for key, st in storages}
+        host = self._ph if self.sharded else self._ensure_host()
+        return [DigestEntry(r.name, by_ptr.get(host[r.name].untyped_storage().data_ptr(), ""),
+                            dtype_name(r.data.dtype), r.full_numel, values[i] if values else 0)
+                for i, r in enumerate(self.regions)]
+
+    def _add_digest_record(self, w, storages, inf: _InFlight) -> None:
+        """Single writer: the record as one more member of the archive. GPU: the pinned block,
+        whose value slots the snapshot stream fills before the drain event the writer waits on;
+        everything else in it is written here (disjoint bytes). CPU: plain bytes."""
+        if not self.is_cuda:
+            w.add_bytes(RECORD_NAME, pack_record(self._digest_entries(storages, self._dg_cpu)))
+            return
+        rec = pack_record(self._digest_entries(storages, None))
+        block = self._dg_host
+        slots = [self._dg_slot(i) for i in range(len(self.regions))]
+        pos = 0
+        for lo in slots + [len(rec)]:
+            if lo > pos:
+                block[pos:lo] = torch.frombuffer(bytearray(rec[pos:lo]), dtype=torch.uint8)
+            pos = lo + 8
+        w.add_buffer(RECORD_NAME, block.data_ptr(), len(rec))
+        inf.keep.append(block)
 
     # ------------------------------------------------------------------ sharded save
     def _save_sharded(self, path: str, tmp: str, build_state, ev, inf: _InFlight) -> None:
@@ -347,6 +421,13 @@ class CheckpointEngine:
                     inf.keep.append(storage)
             for name, data in small[4:]:
                 zw.add_bytes(name, data)
+            dg_entries = None
+            if self.digest:
+                # a fixed-size external record: rank 0 writes it once every rank's values are in
+                self._ph = ph
+                dg_entries = self._digest_entries(storages, None)
+                zw.add_external(RECORD_NAME, record_size(len(dg_entries)), 0)
+            dg_off = next((off for name, off, _size in zw.layout_records() if name == RECORD_NAME), None)
             offs = {ext[name]: (name, off) for name, off, _size in zw.layout_records() if name in ext}
             if set(offs) != {r.name for r in self.regions}:
                 raise RuntimeError(f"sharded save: state dict does not view every region ({sorted(offs)})")
@@ -361,9 +442,12 @@ class CheckpointEngine:
         nthreads = self.writer_threads
         fsync = self.fsync
         stats = inf.stats
+        want_digest = self.digest
+        dg_cpu, dg_host = self._dg_cpu, self._dg_host
 
         def _run():
             err = ""
+            dg = None
             try:
                 box = [offs]
                 dist.broadcast_object_list(box, src=0, group=group)
@@ -382,11 +466,14 @@ class CheckpointEngine:
                 crcs = rt.write_pieces(tmp, file_offs, ptrs, lens, nthreads, handle, fsync, True)
                 stats.write_s = time.perf_counter() - t_w
                 mine = [(rec, lo, ln, c) for (rec, lo, ln), c in zip(meta, crcs)]
+                if want_digest:  # write_pieces has waited for the drain event: the values are in
+                    dg = dg_cpu if dg_host is None else \
+                        [v & MASK64 for v in dg_host.view(torch.int64).tolist()]
             except Exception as e:  # report to rank 0, keep the collectives in step
                 err = f"rank {rank}: {e!r}"
                 mine = []
             gathered = [None] * dist.get_world_size(group) if rank == 0 else None
-            dist.gather_object((err, mine), gathered, dst=0, group=group)
+            dist.gather_object((err, mine, dg), gathered, dst=0, group=group)
             status = ""
             if rank == 0:
                 errs = [g[0] for g in gathered if g[0]]
@@ -394,7 +481,7 @@ class CheckpointEngine:
                     if errs:
                         raise RuntimeError("; ".join(errs))
                     per = {}
-                    for _e, pieces in gathered:
+                    for _e, pieces, _dg in gathered:
                         for rec, lo, ln, c in pieces:
                             per.setdefault(rec, []).append((lo, ln, c))
                     for rec, sizes in ((n, s_) for n, _o, s_ in zw.layout_records() if n in per):
@@ -408,6 +495,16 @@ class CheckpointEngine:
                         if pos != sizes:
                             raise RuntimeError(f"{rec}: pieces cover {pos} of {sizes} bytes")
                         zw.set_external_crc(rec, crc)
+                    if dg_entries is not None:
+                        for i, e in enumerate(dg_entries):
+                            e.digest = sum(g[2][i] for g in gathered) & MASK64
+                        raw = pack_record(dg_entries)
+                        fd = os.open(tmp, os.O_WRONLY)
+                        try:
+                            os.pwrite(fd, raw, dg_off)
+                        finally:
+                            os.close(fd)
+                        zw.set_external_crc(RECORD_NAME, zlib.crc32(raw) & 0xFFFFFFFF)
                     t_f = time.perf_counter()
                     zw.run_sync(0, fsync)
                     ws = zw.wait()

@@ -345,6 +345,9 @@ def train(args) -> int:
             return
         from .utils.digest import state_digest
 
+        # the last step's AdamW buckets run on the optimizer stream; nothing after the final step
+        # makes this stream wait for them, and the digest kernel is quick enough to overtake them
+        optimizer.gate.wait_all()
         dg = state_digest(model.flat.params, optimizer.exp_avg, optimizer.exp_avg_sq)
         # the loader position a checkpoint at this step boundary records (the live loader may
         # already have fetched the next batch when a signal stops the run)
@@ -353,8 +356,35 @@ def train(args) -> int:
                     f"exp_avg={dg['exp_avg']} exp_avg_sq={dg['exp_avg_sq']} "
                     f"optimizer_step={optimizer.step_count} data_loader={json.dumps(pos, sort_keys=True)}")
 
+    def verify_resumed_state() -> None:
+        """The restored buffers, digested where they now live, against the digest record of the
+        file they came from. A mismatch stops the job here: before it trains on the state, writes
+        a checkpoint of it or prunes the file (ckpt/verify.py)."""
+        from .ckpt.verify import CheckpointCorrupt, read_digest_record, verify_restored
+
+        record = read_digest_record(resume_file)
+        if info.world_size > 1:
+            # every rank digests its own pieces (ZeRO-1: the shards it owns); the partial digests
+            # add up over the gloo control group, so all ranks see one value and leave together
+            regions = shard_regions(model, optimizer, info.rank, info.world_size)
+            live = {r.name: [(r.data[off : off + n], lo) for lo, off, n in r.pieces] for r in regions}
+            numels = {r.name: r.full_numel for r in regions}
+            group = info.ctrl_group
+        else:
+            live = {"params": model.flat.params, "exp_avg": optimizer.exp_avg, "exp_avg_sq": optimizer.exp_avg_sq}
+            numels, group = None, None
+        try:
+            ok = verify_restored(record, live, group=group, path=resume_file, numels=numels, log=logger.info)
+        except CheckpointCorrupt as e:
+            logger.error(f"[CHECKPOINT] {e}; not training on it (the file is left in place)")
+            raise
+        if ok:
+            logger.info("Checkpoint digest verified: " + " ".join(f"{k}={v}" for k, v in ok.items()))
+
     if checkpoint is not None:
         training_step = int(checkpoint["training_step"])
+        if not getattr(args, "no_verify_checkpoint", False):
+            verify_resumed_state()
         logger.info(f"Resuming training from training_step {training_step}")
         log_digest(training_step, " (resumed)")
     else:
@@ -409,6 +439,7 @@ def train(args) -> int:
         except FileNotFoundError:
             pass
     sharded = info.world_size > 1
+    ckpt_digest = not getattr(args, "no_checkpoint_digest", False)  # a state_digest record in every file
 
     def ckpt_engine():
         if ckpt["engine"] is None:
@@ -418,11 +449,11 @@ def train(args) -> int:
                 ckpt["engine"] = CheckpointEngine(regions, mode=args.checkpoint_mode,
                                                   writer_threads=args.checkpoint_writer_threads,
                                                   group=info.ckpt_group, rank=info.rank, world=info.world_size,
-                                                  sharded=True)
+                                                  sharded=True, digest=ckpt_digest)
             else:
                 ckpt["engine"] = CheckpointEngine(
                     {"params": model.flat.params, "exp_avg": optimizer.exp_avg, "exp_avg_sq": optimizer.exp_avg_sq},
-                    mode=args.checkpoint_mode, writer_threads=args.checkpoint_writer_threads)
+                    mode=args.checkpoint_mode, writer_threads=args.checkpoint_writer_threads, digest=ckpt_digest)
         return ckpt["engine"]
 
     if not args.no_checkpoint_prealloc:
@@ -474,7 +505,7 @@ def train(args) -> int:
 
         solo = CheckpointEngine({"params": model.flat.params, "exp_avg": optimizer.exp_avg,
                                  "exp_avg_sq": optimizer.exp_avg_sq}, mode="host",
-                                writer_threads=args.checkpoint_writer_threads)
+                                writer_threads=args.checkpoint_writer_threads, digest=ckpt_digest)
         # (the lock file stays: a slower survivor must not write the file a second time)
         return solo.save(ckpt_path, build, step=step_now, blocking=True)
 

@@ -165,6 +165,18 @@ def build_parser() -> argparse.ArgumentParser:
         help="Pin the checkpoint host buffers at the first save instead of in a background thread at startup",
     )
     parser.add_argument(
+        "--no-checkpoint-digest",
+        action="store_true",
+        help="Write checkpoints without the state_digest record (the per-buffer digests a resume and "
+        "`python -m fault_tolerant_llm_training_amd.ckpt verify` check the state against)",
+    )
+    parser.add_argument(
+        "--no-verify-checkpoint",
+        action="store_true",
+        help="On resume, do not compare the restored parameters and AdamW moments with the digests "
+        "recorded in the checkpoint (by default a mismatch stops the job before it trains)",
+    )
+    parser.add_argument(
         "--checkpoint-writer-threads", type=int, default=8, help="Parallel pwrite threads of the checkpoint writer"
     )
     parser.add_argument(
