@@ -17,6 +17,7 @@
 // flat buffer, so a step is two reduction launches + one streaming launch over
 // ~8e9 elements instead of ~300-tensor foreach chains.
 #include "torch_utils.h"
+#include "sround.h"
 
 #include <vector>
 
@@ -61,6 +62,12 @@ struct V8 {
     const P8<E> r = pk8<E>(f);
     st16<NT>(p, r.v[0]);
     if constexpr (!E::is16) st16<NT>(p + 4, r.v[1]);
+  }
+  // bf16 storage only: the 8 elements of flat vector c rounded stochastically (sround.h)
+  __device__ static void store_sr(typename E::T* p, const float* f, uint32_t key_lo, uint32_t key_hi,
+                                  uint32_t step, uint32_t buffer, uint64_t c) {
+    static_assert(std::is_same<E, EBF16>::value, "stochastic rounding: bf16 storage only");
+    st16<NT>(p, sr_pack8(f, key_lo, key_hi, step, buffer, c));
   }
 };
 
@@ -120,7 +127,9 @@ __global__ __launch_bounds__(1024) void norm_finish_kernel(const float* __restri
   }
 }
 
-template <class P, class S, bool NT>
+// SR: the stores whose storage type is bf16 round stochastically (sround.h) with the random bits of
+// (sr.key, step, buffer, flat vector index sr.c0 + i); fp32 moments are stored as without it.
+template <class P, class S, bool NT, bool SR>
 __global__ __launch_bounds__(256) void adamw_kernel(typename P::T* __restrict__ p,
                                                     const typename P::T* __restrict__ g,
                                                     typename S::T* __restrict__ m,
@@ -129,7 +138,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(typename P::T* __restrict__ 
                                                     float eps, float wd, float inv_bc1,
                                                     float inv_sqrt_bc2,
                                                     const float* __restrict__ stats,
-                                                    const float* __restrict__ hyper, int exact) {
+                                                    const float* __restrict__ hyper, int exact,
+                                                    SrArgs sr) {
   if (stats[2] != 0.f) return;  // non-finite gradient norm: skip the whole update
   if (hyper != nullptr) {
     // [lr, 1/bc1, 1/sqrt(bc2)] from device memory: a HIP-graph replay of the optimizer reads
@@ -162,9 +172,46 @@ __global__ __launch_bounds__(256) void adamw_kernel(typename P::T* __restrict__ 
         pf[j] -= step * mf[j] * fast_rcp(denom);
       }
     }
-    V8<P, NT>::store(p + i * 8, pf);
-    V8<S, NT>::store(m + i * 8, mf);
-    V8<S, NT>::store(v + i * 8, vf);
+    if constexpr (SR) {
+      const uint64_t c = sr.c0 + (uint64_t)i;
+      V8<P, NT>::store_sr(p + i * 8, pf, sr.key_lo, sr.key_hi, sr.step, SR_BUF_PARAM, c);
+      if constexpr (std::is_same<S, EBF16>::value) {
+        V8<S, NT>::store_sr(m + i * 8, mf, sr.key_lo, sr.key_hi, sr.step, SR_BUF_EXP_AVG, c);
+        V8<S, NT>::store_sr(v + i * 8, vf, sr.key_lo, sr.key_hi, sr.step, SR_BUF_EXP_AVG_SQ, c);
+      } else {
+        V8<S, NT>::store(m + i * 8, mf);
+        V8<S, NT>::store(v + i * 8, vf);
+      }
+    } else {
+      V8<P, NT>::store(p + i * 8, pf);
+      V8<S, NT>::store(m + i * 8, mf);
+      V8<S, NT>::store(v + i * 8, vf);
+    }
+  }
+}
+
+// out[i] = x[i] rounded with the random bits of (key, step, buffer, flat index 8 * c0 + i): the
+// same sr_pack8 / sr_bits8 / sr_bf16 the AdamW stores use, on its own (tests, utils/sround.py's
+// device twin). One 8-element vector per thread; a last partial vector element by element.
+__global__ __launch_bounds__(256) void sr_round_kernel(const float* __restrict__ x,
+                                                       bf16_t* __restrict__ out, long n,
+                                                       uint32_t buffer, SrArgs sr) {
+  const long n8 = n >> 3;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i * 8 < n; i += (long)gridDim.x * 256) {
+    const uint64_t c = sr.c0 + (uint64_t)i;
+    if (i < n8) {
+      float f[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] = x[i * 8 + j];
+      *reinterpret_cast<uint4*>(out + i * 8) = sr_pack8(f, sr.key_lo, sr.key_hi, sr.step, buffer, c);
+    } else {
+      const uint4 w = sr_bits8(sr.key_lo, sr.key_hi, sr.step, buffer, c);
+      const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+      for (long e = i * 8; e < n; ++e) {
+        const int j = (int)(e & 7);
+        out[e] = sr_bf16(x[e], (ws[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+      }
+    }
   }
 }
 
@@ -188,6 +235,15 @@ void launch_sumsq(const at::Tensor& grad, long n8, int nb, float* partial) {
   });
 }
 
+SrArgs make_sr_args(int64_t key, int64_t step, int64_t offset) {
+  SrArgs sr;
+  sr.key_lo = (uint32_t)((uint64_t)key & 0xffffffffu);
+  sr.key_hi = (uint32_t)((uint64_t)key >> 32);
+  sr.step = (uint32_t)((uint64_t)step & 0xffffffffu);
+  sr.c0 = (uint64_t)offset >> 3;
+  return sr;
+}
+
 }  // namespace
 
 // Writes [norm, coef, nonfinite] into stats (fp32[3], device).
@@ -209,13 +265,25 @@ void grad_norm_(const at::Tensor& grad, const at::Tensor& stats, double max_norm
 
 void adamw_(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const at::Tensor& v,
             const at::Tensor& stats, double lr, double beta1, double beta2, double eps, double wd,
-            int64_t step, int64_t max_blocks, const std::optional<at::Tensor>& hyper) {
+            int64_t step, int64_t max_blocks, const std::optional<at::Tensor>& hyper,
+            bool stochastic_rounding, int64_t key, int64_t offset) {
   const float* hp = nullptr;
   if (hyper.has_value() && hyper->defined()) {
     FT_CHECK_F32((*hyper));
     TORCH_CHECK(hyper->is_cuda() && hyper->numel() >= 3, "adamw: hyper must be a device fp32[3]");
+    // the step number of the random bits is a launch argument: a captured launch would replay one
+    // step's noise for ever
+    TORCH_CHECK(!stochastic_rounding, "adamw: stochastic rounding is not supported with device "
+                "hyper-parameters (graph replay)");
     hp = cptr<float>(*hyper);
   }
+  if (stochastic_rounding) {
+    TORCH_CHECK(p.scalar_type() == at::kBFloat16,
+                "adamw: stochastic rounding supports bf16 parameters only, got ", p.scalar_type());
+    TORCH_CHECK(offset >= 0 && offset % 8 == 0,
+                "adamw: offset (flat index of p[0]) must be a non-negative multiple of 8");
+  }
+  const SrArgs sr = make_sr_args(key, step, offset);
   FT_CHECK_CUDA(p);
   FT_CHECK_CONTIG(p);
   FT_CHECK_CONTIG(g);
@@ -246,27 +314,52 @@ void adamw_(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const
   // hardware v_rcp_f32 / v_sqrt_f32 (1 ulp) are below bf16/fp16 storage rounding but not below
   // fp32's, where torch AdamW's exact math is the parity target (docs/PARITY.md)
   const int exact = (int)ft_exact_math() || p.scalar_type() == at::kFloat;
-  auto go = [&](auto ptag, auto stag) {
+  auto go = [&](auto ptag, auto stag, auto srtag) {
     using P = decltype(ptag);
     using S = decltype(stag);
     using PT = typename P::T;
     using ST = typename S::T;
+    constexpr bool SR = decltype(srtag)::value;
     if (nt)
-      hipLaunchKernelGGL((adamw_kernel<P, S, true>), grid, block, 0, ft_stream(), mptr<PT>(p),
+      hipLaunchKernelGGL((adamw_kernel<P, S, true, SR>), grid, block, 0, ft_stream(), mptr<PT>(p),
                          cptr<PT>(g), mptr<ST>(m), mptr<ST>(v), n8, (float)lr, (float)beta1,
                          (float)beta2, (float)eps, (float)wd, inv_bc1, inv_sqrt_bc2,
-                         cptr<float>(stats), hp, exact);
+                         cptr<float>(stats), hp, exact, sr);
     else
-      hipLaunchKernelGGL((adamw_kernel<P, S, false>), grid, block, 0, ft_stream(), mptr<PT>(p),
+      hipLaunchKernelGGL((adamw_kernel<P, S, false, SR>), grid, block, 0, ft_stream(), mptr<PT>(p),
                          cptr<PT>(g), mptr<ST>(m), mptr<ST>(v), n8, (float)lr, (float)beta1,
                          (float)beta2, (float)eps, (float)wd, inv_bc1, inv_sqrt_bc2,
-                         cptr<float>(stats), hp, exact);
+                         cptr<float>(stats), hp, exact, sr);
   };
-  FT_DISPATCH_E(p.scalar_type(), {
-    if (m.scalar_type() == at::kFloat) go(E{}, EF32{});
-    else go(E{}, E{});
-  });
+  if (stochastic_rounding) {  // bf16 parameters (checked above); moments bf16 or fp32
+    if (m.scalar_type() == at::kFloat) go(EBF16{}, EF32{}, std::true_type{});
+    else go(EBF16{}, EBF16{}, std::true_type{});
+  } else {
+    FT_DISPATCH_E(p.scalar_type(), {
+      if (m.scalar_type() == at::kFloat) go(E{}, EF32{}, std::false_type{});
+      else go(E{}, E{}, std::false_type{});
+    });
+  }
   FT_LAUNCH_CHECK();
+}
+
+// x (fp32) -> bf16 by stochastic rounding with the bits of (key, step, buffer, offset + i): the
+// device function of the AdamW stores (sround.h) on its own.
+at::Tensor sr_round_bf16(const at::Tensor& x, int64_t key, int64_t step, int64_t buffer, int64_t offset) {
+  FT_CHECK_CUDA(x);
+  FT_CHECK_CONTIG(x);
+  FT_CHECK_F32(x);
+  TORCH_CHECK(buffer >= 0 && buffer <= 2, "sr_round_bf16: buffer is 0 (params), 1 (exp_avg) or 2 (exp_avg_sq)");
+  TORCH_CHECK(offset >= 0 && offset % 8 == 0, "sr_round_bf16: offset must be a non-negative multiple of 8");
+  const at::DeviceGuard guard(x.device());
+  auto out = at::empty(x.sizes(), x.options().dtype(at::kBFloat16));
+  const long n = x.numel();
+  if (n == 0) return out;
+  const int nb = stream_grid((n + 7) / 8);
+  hipLaunchKernelGGL(sr_round_kernel, dim3(nb), dim3(256), 0, ft_stream(), cptr<float>(x),
+                     mptr<bf16_t>(out), n, (uint32_t)buffer, make_sr_args(key, step, offset));
+  FT_LAUNCH_CHECK();
+  return out;
 }
 
 // Per-bucket partial sums of squares, launched while backward is still running:
@@ -320,6 +413,8 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
   m.def("grad_norm_(Tensor grad, Tensor(a!) stats, float max_norm) -> ()", &grad_norm_);
   m.def(
       "adamw_(Tensor(a!) p, Tensor g, Tensor(b!) m, Tensor(c!) v, Tensor stats, float lr, float "
-      "beta1, float beta2, float eps, float wd, int step, int max_blocks=0, Tensor? hyper=None) -> ()",
+      "beta1, float beta2, float eps, float wd, int step, int max_blocks=0, Tensor? hyper=None, "
+      "bool stochastic_rounding=False, int key=0, int offset=0) -> ()",
       &adamw_);
+  m.def("sr_round_bf16(Tensor x_f32, int key, int step, int buffer, int offset) -> Tensor", &sr_round_bf16);
 }

@@ -44,6 +44,11 @@ def hw_queue_problem() -> str:
 class GraphedStep:
     def __init__(self, model, reducer, optimizer, lr_scheduler,
                  fwd_bwd: Callable[[torch.Tensor, torch.Tensor], torch.Tensor]):
+        if getattr(optimizer, "stochastic_rounding", False):
+            # the random bits are keyed by the step number, a launch argument: a captured launch
+            # would replay one step's noise for ever
+            raise ValueError("stochastic rounding (--stochastic-rounding) is not supported under "
+                             "whole-step graph replay (--hip-graph / --compile)")
         self.model, self.red, self.opt, self.sched = model, reducer, optimizer, lr_scheduler
         self.fwd_bwd = fwd_bwd
         self.graph: Optional[torch.cuda.CUDAGraph] = None

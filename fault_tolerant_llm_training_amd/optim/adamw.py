@@ -90,7 +90,8 @@ class FlatAdamW(torch.optim.Optimizer):
 
     def __init__(self, params, flat: FlatParamSpace, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 1e-2, state_dtype: Optional[torch.dtype] = None,
-                 max_grad_norm: float = 0.0, fused: bool = True, reducer=None):
+                 max_grad_norm: float = 0.0, fused: bool = True, reducer=None,
+                 stochastic_rounding: bool = False, sr_seed: int = 0):
         params = list(params)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False,
@@ -104,6 +105,16 @@ class FlatAdamW(torch.optim.Optimizer):
         self.exp_avg = torch.zeros(n, dtype=sd, device=flat.device)
         self.exp_avg_sq = torch.zeros(n, dtype=sd, device=flat.device)
         self.step_count = 0
+        # --stochastic-rounding: the bf16 stores of the update round up or down at random, with bits
+        # that are a pure function of (sr_key, step_count, buffer, flat element index) -- no generator
+        # state, so a resume, any launch partitioning and ZeRO-1 shards give the same bits
+        # (utils/sround.py, csrc/kernels/sround.h). A resume puts the checkpoint's key into sr_key.
+        self.stochastic_rounding = bool(stochastic_rounding)
+        if self.stochastic_rounding and flat.dtype != torch.bfloat16:
+            raise ValueError(f"stochastic rounding supports bf16 parameters only, got {flat.dtype}")
+        from ..utils.sround import key_from_seed
+
+        self.sr_key = key_from_seed(sr_seed)
         self.max_grad_norm = float(max_grad_norm)
         self.stats = torch.zeros(3, dtype=torch.float32, device=flat.device)  # norm, coef, nonfinite
         # ring of per-step host copies: step -> (pinned [3] copy, event or None)
@@ -165,12 +176,21 @@ class FlatAdamW(torch.optim.Optimizer):
                                            np.float32(1.0) / np.sqrt(bc2)], dtype=np.float32)))
         self.hyper.copy_(h, non_blocking=True)
 
-    def _update(self, p, g, m, v, lr, b1, b2, eps, wd, max_blocks: int = 0):
+    def _update(self, p, g, m, v, lr, b1, b2, eps, wd, max_blocks: int = 0, offset: int = 0):
+        """One AdamW launch over a piece of the flat buffers; ``offset``: the flat index of ``p[0]``
+        (what the stochastic-rounding bits are indexed by, for the moments too)."""
         if native(p):
-            kernels().adamw_(p, g, m, v, self.stats, lr, b1, b2, eps, wd, self.step_count, max_blocks,
-                             self.hyper if self.graph_mode else None)
+            if self.stochastic_rounding:
+                if self.graph_mode:  # the step number of the bits would be baked in at capture
+                    raise RuntimeError("stochastic rounding is not supported under whole-step graph replay")
+                kernels().adamw_(p, g, m, v, self.stats, lr, b1, b2, eps, wd, self.step_count, max_blocks,
+                                 None, True, self.sr_key, offset)
+            else:
+                kernels().adamw_(p, g, m, v, self.stats, lr, b1, b2, eps, wd, self.step_count, max_blocks,
+                                 self.hyper if self.graph_mode else None)
         else:
-            _adamw_reference(p, g, m, v, self.stats, lr, b1, b2, eps, wd, self.step_count)
+            _adamw_reference(p, g, m, v, self.stats, lr, b1, b2, eps, wd, self.step_count,
+                             sr=(self.sr_key, offset) if self.stochastic_rounding else None)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -207,7 +227,7 @@ class FlatAdamW(torch.optim.Optimizer):
                 slo, shi = r.state_range(b)
                 self._update(r.param_for_update(b), r.grad_for_update(b), self.exp_avg[slo:shi],
                              self.exp_avg_sq[slo:shi], lr, b1, b2, eps, wd,
-                             self.overlap_blocks if r.overlap else 0)
+                             self.overlap_blocks if r.overlap else 0, offset=r.update_offset(b))
                 if self.zero1 and r.dry_comm:
                     pass
                 elif self.zero1 and r.single_stream and r.overlap:
@@ -417,11 +437,15 @@ def _norm_reference(sumsq: torch.Tensor, stats: torch.Tensor, max_norm: float) -
     stats.copy_(torch.tensor([norm, coef, 1.0 if sticky else 0.0]))
 
 
-def _adamw_reference(p, g, m, v, stats, lr, b1, b2, eps, wd, step):
+def _adamw_reference(p, g, m, v, stats, lr, b1, b2, eps, wd, step, sr=None):
     """Reference of the fused kernel (fp32 math, storage dtype rounding); fp64 parameters (the
-    composed path of --model-dtype fp64) are updated in fp64, as the reference's torch AdamW does."""
+    composed path of --model-dtype fp64) are updated in fp64, as the reference's torch AdamW does.
+    ``sr = (key, offset)``: stochastic rounding of the bf16 stores (utils/sround.py), ``offset``
+    the flat index of ``p[0]``; fp32 moments are stored as without it."""
     if stats[2].item() != 0:
         return
+    if sr is not None and p.dtype != torch.bfloat16:
+        raise ValueError(f"stochastic rounding supports bf16 parameters only, got {p.dtype}")
     coef = stats[1].item()
     md = torch.float64 if p.dtype == torch.float64 else torch.float32
     gf = g.to(md) * coef
@@ -434,6 +458,13 @@ def _adamw_reference(p, g, m, v, stats, lr, b1, b2, eps, wd, step):
     bc2 = 1 - b2 ** step
     denom = vf.sqrt() / math.sqrt(bc2) + eps
     pf.sub_((lr / bc1) * mf / denom)
+    if sr is not None:
+        from ..utils.sround import BUF_EXP_AVG, BUF_EXP_AVG_SQ, BUF_PARAM, sr_round_bf16
+
+        key, offset = sr
+        for dst, src, buf in ((p, pf, BUF_PARAM), (m, mf, BUF_EXP_AVG), (v, vf, BUF_EXP_AVG_SQ)):
+            dst.copy_(sr_round_bf16(src.cpu(), key, step, buf, offset) if dst.dtype == torch.bfloat16 else src)
+        return
     p.copy_(pf)
     m.copy_(mf)
     v.copy_(vf)

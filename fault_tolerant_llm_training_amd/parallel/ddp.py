@@ -339,6 +339,11 @@ class GradReducer:
     def param_for_update(self, b: Bucket) -> torch.Tensor:
         return self.param_shard(b) if self.mode == "zero1" else self.flat.params[b.lo : b.hi]
 
+    def update_offset(self, b: Bucket) -> int:
+        """Flat index of the first element of :meth:`param_for_update` (b): what the optimizer's
+        stochastic-rounding bits are indexed by, so every mode and bucket size rounds alike."""
+        return b.lo + self.rank * b.shard_len if self.mode == "zero1" else b.lo
+
     def state_range(self, b: Bucket):
         """(lo, hi) of bucket b in the optimizer-state buffers of this rank."""
         if self.mode == "zero1":

@@ -320,9 +320,28 @@ def train(args) -> int:
         state_dtype = torch.float32 if model_dtype == torch.float16 else None
     reducer = GradReducer(model.flat, model.sinks_in_backward_order(), bucket_mb=args.dp_bucket_mb,
                           mode=args.dp_mode or None, reduce_dtype=args.dp_reduce_dtype)
+    sr_on = bool(getattr(args, "stochastic_rounding", False))
+    if sr_on and model_dtype != torch.bfloat16:
+        raise ValueError("--stochastic-rounding supports bf16 parameters only (--model-dtype bf16)")
     optimizer = FlatAdamW(model.parameters(), model.flat, lr=args.learning_rate, state_dtype=state_dtype,
-                          max_grad_norm=args.grad_max_norm, fused=args.fused_optimizer, reducer=reducer)
+                          max_grad_norm=args.grad_max_norm, fused=args.fused_optimizer, reducer=reducer,
+                          stochastic_rounding=sr_on, sr_seed=args.seed)
     model.gate = optimizer.gate
+    if sr_on:
+        recorded = (checkpoint.get("meta") or {}).get("sr_key") if checkpoint is not None else None
+        if recorded is not None:
+            # the noise stream of the run being resumed: the same bits an uninterrupted run draws
+            if int(recorded) != optimizer.sr_key:
+                logger.info(f"Stochastic rounding: the checkpoint records key {int(recorded):#018x}, --seed "
+                            f"{args.seed} gives {optimizer.sr_key:#018x}; continuing with the recorded key")
+            optimizer.sr_key = int(recorded)
+        elif checkpoint is not None:
+            logger.info("Stochastic rounding: the checkpoint records no key (written without the flag); "
+                        "deriving it from --seed")
+        stores = "params, exp_avg, exp_avg_sq" if optimizer.exp_avg.dtype == torch.bfloat16 else "params; fp32 moments as is"
+        logger.info(f"Stochastic rounding: on -- AdamW rounds its bf16 stores ({stores}) up or down at random, "
+                    f"exact in expectation; key {optimizer.sr_key:#018x}, random bits a function of "
+                    "(key, optimizer step, buffer, flat element index)")
     if checkpoint is not None:
         optimizer.load_state_dict(checkpoint["optimizer"])
         logger.info("Optimizer loaded from checkpoint")
@@ -440,6 +459,9 @@ def train(args) -> int:
             pass
     sharded = info.world_size > 1
     ckpt_digest = not getattr(args, "no_checkpoint_digest", False)  # a state_digest record in every file
+    run_meta = {"world_size": info.world_size, "job_id": str(job_id)}
+    if sr_on:  # (files written without the flag carry neither entry)
+        run_meta.update(stochastic_rounding=True, sr_key=int(optimizer.sr_key))
 
     def ckpt_engine():
         if ckpt["engine"] is None:
@@ -471,7 +493,7 @@ def train(args) -> int:
         def build(host):
             return build_checkpoint(model, optimizer, lr_scheduler, step_now, host,
                                     data_loader=states if info.distributed else states[0], rng=rng,
-                                    extra_meta={"world_size": info.world_size, "job_id": str(job_id)})
+                                    extra_meta=dict(run_meta))
 
         engine = ckpt_engine()
         writes = sharded or info.is_main
@@ -501,7 +523,7 @@ def train(args) -> int:
         def build(host):
             return build_checkpoint(model, optimizer, lr_scheduler, step_now, host,
                                     data_loader=states if info.distributed else states[0], rng=rng,
-                                    extra_meta={"world_size": info.world_size, "job_id": str(job_id)})
+                                    extra_meta=dict(run_meta))
 
         solo = CheckpointEngine({"params": model.flat.params, "exp_avg": optimizer.exp_avg,
                                  "exp_avg_sq": optimizer.exp_avg_sq}, mode="host",

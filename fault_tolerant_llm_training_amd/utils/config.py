@@ -259,6 +259,15 @@ def build_parser() -> argparse.ArgumentParser:
         "causal attention across the whole sample, as the reference)",
     )
     parser.add_argument(
+        "--stochastic-rounding",
+        action="store_true",
+        help="AdamW stores its bf16 parameters and moments with stochastic rounding instead of "
+        "round-to-nearest, so updates below half a bf16 spacing accumulate in expectation instead of "
+        "being dropped. The random bits are a pure function of (--seed key, optimizer step, buffer, flat "
+        "element index): a resume and every data-parallel mode stay bit-reproducible. "
+        "bf16 parameters only (--model-dtype bf16); not with --hip-graph / --compile",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -279,4 +288,12 @@ def build_parser() -> argparse.ArgumentParser:
 
 def get_args(argv=None) -> argparse.Namespace:
     """Parse flags (reference ``utils.py:112-203``)."""
-    return build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.stochastic_rounding and args.model_dtype != "bf16":
+        parser.error(f"--stochastic-rounding supports bf16 parameters only (--model-dtype bf16), "
+                     f"got --model-dtype {args.model_dtype}")
+    if args.stochastic_rounding and (args.hip_graph or args.compile):
+        parser.error("--stochastic-rounding is not supported under whole-step graph replay "
+                     "(--hip-graph / --compile): run the step eagerly")
+    return args

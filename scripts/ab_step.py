@@ -33,6 +33,8 @@ Knobs toggled between timing windows (alternating rounds, so box and clock drift
   cumask — the optimizer side stream (norm + AdamW) confined to every 4th CU (hipExtStreamCreateWithCUMask)
   cumask2 — ... to every 2nd CU
   f32mfma — (--dtype fp32) the fp32 model's GEMMs on the fp32 MFMA kernel instead of hipBLASLt
+  sr    — (--dtype bf16) AdamW stores its bf16 parameters and moments with stochastic rounding
+          (--stochastic-rounding; csrc/kernels/sround.h) instead of round-to-nearest
 Usage: python scripts/ab_step.py [--steps 8] [--rounds 3] [--configs gemm,dw ...]
 """
 from __future__ import annotations
@@ -129,6 +131,8 @@ def main():
                "raster": lambda on: (torch.cuda.synchronize(), kernels().gemm_w4_set_group(-1 if on else 0)),
                "deadzero": lambda on: (torch.cuda.synchronize(), kernels().gemm_w4_set_deadzero(1 if on else 0)),
                "f32mfma": lambda on: (torch.cuda.synchronize(), Fx.set_f32_mfma(on)),
+               "sr": lambda on: (opt.gate.wait_all(), torch.cuda.synchronize(),
+                                 setattr(opt, "stochastic_rounding", bool(on))),
                "remainder": lambda on: (torch.cuda.synchronize(), kernels().gemm_w4_set_remainder(1 if on else 0))}
     side0 = red.side
     masked = {}
