@@ -308,6 +308,39 @@ class Transformer(nn.Module):
             inv_count = (1.0 / n.float()).to(h.device)
         return Fx.lm_head_cross_entropy(h, self.output.weight, labels, inv_count, sk(self.output.weight))
 
+    @torch.no_grad()
+    def evaluate(self, tokens: torch.Tensor, labels: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
+        """Forward only: ``acc`` (int64 [4] on the model's device) += the evaluation counters of this
+        batch (fixed-point NLL sum, tokens, top-1 hits, left-out rows; utils/evalacc.py).
+
+        The same embedding, blocks, final norm, per-layer parameter-gate waits and document mask as
+        :meth:`forward`, on the same kernels, then the forward-only head (``Fx.lm_head_eval``)
+        instead of ``LMHeadCrossEntropyFn``, which forms the head's gradients in its forward. No
+        autograd graph is built, every block runs plain (never through activation checkpointing) and
+        no block is handed its kept-attention store, so nothing of the training state is written:
+        not the flat gradient buffer, not a sink's norm partials or flags, not the reducer's bucket
+        state. Only ``_gen`` advances, which invalidates nothing (a kept attention output is
+        consumed by the backward of the forward that stored it)."""
+        B, S = tokens.shape
+        emb_r, layer_r, final_r = self._ranges
+        self._wait(emb_r)
+        h = Fx.embedding(tokens, self.tok_embeddings.weight, None)
+        cos, sin = self.rope_cos, self.rope_sin
+        doc = None if self.doc_bos is None else Fx.doc_bounds(tokens, self.doc_bos)
+        d = None
+        self._gen += 1
+        for i, layer in enumerate(self.layers.values()):
+            self._wait(layer_r[i])
+            h, d = layer(h, d, cos, sin, S, None, doc)
+        self._wait(final_r)
+        a = self.model_args
+        ln = a.norm_type == "layernorm"
+        if d is None:
+            h = Fx.norm(h, self.norm.weight, None, a.norm_eps, ln)
+        else:
+            _, h = Fx.add_norm(h, d, self.norm.weight, None, a.norm_eps, ln)
+        return Fx.lm_head_eval(h, self.output.weight, labels, acc)
+
     def num_params(self) -> int:
         return sum(p.numel() for p in self.parameters())
 

@@ -840,6 +840,32 @@ def lm_head_cross_entropy(h, weight, labels, inv_count, sink=None):
     return LMHeadCrossEntropyFn.apply(h, weight, sink, labels, inv_count)
 
 
+@torch.no_grad()
+def lm_head_eval(h, weight, labels, acc):
+    """Forward-only LM head for evaluation: ``acc`` (int64 [4] on ``h``'s device) += the fixed-point
+    NLL sum, token count, top-1 hits and left-out rows of these tokens (utils/evalacc.py has the
+    definition). Chunked over rows like the training head: per chunk the logits are formed, read
+    once by ``xent_eval_`` and freed. No gradient is formed and no :class:`GradSink` is involved,
+    so unlike :class:`LMHeadCrossEntropyFn` this never writes the flat gradient buffer."""
+    D = h.shape[-1]
+    h2 = h.reshape(-1, D)
+    lab = labels.reshape(-1)
+    if not native(h):
+        from ..utils.evalacc import xent_eval_reference_
+
+        return xent_eval_reference_(torch.mm(h2, weight.t()), lab, acc, IGNORE_INDEX)
+    K_ = kernels()
+    h2 = h2.contiguous()
+    lab = lab.contiguous()
+    T, V = h2.shape[0], weight.shape[0]
+    rows = _head_rows(T, V)
+    for r0 in range(0, T, rows):
+        logits = _head_fwd(h2[r0 : r0 + rows], weight)
+        K_.xent_eval_(logits, lab[r0 : r0 + rows], acc, IGNORE_INDEX)
+        del logits
+    return acc
+
+
 # attention ops live in ops/attention.py; re-exported for callers of the functional namespace
 from .attention import (  # noqa: E402,F401
     AttentionKeep,

@@ -611,6 +611,40 @@ def train(args) -> int:
 
     boundary.count = 0
     boundary.count_sum = 0.0
+
+    eval_every = int(getattr(args, "eval_every", 0) or 0)
+    eval_set = None
+    if eval_every > 0:
+        from . import evaluation
+
+        eval_set = evaluation.build_eval_set(args, holder["vocab"], info.rank, W, pin=device.type == "cuda")
+        logger.info(eval_set.describe(eval_every))
+
+    def evaluate_at(step_now: int, final: bool = False) -> None:
+        """--eval-every: the held-out set through the forward-only pass, at step boundary ``step_now``
+        (every rank calls it, after the boundary's vote and a periodic save). Rank 0 logs the record.
+        A signal or an error on any rank abandons the evaluation on all of them without a record and
+        stops the run through the boundary's own path: the checkpoint is at ``step_now`` and the
+        resumed job evaluates here again."""
+        nonlocal pending_err
+        complete_pending()  # graph mode: the parameters of this boundary exist after the pending optimizer step
+        logger.info(f"Evaluating at step {step_now}: {eval_set.sequences} sequences")
+        summary, err = evaluation.run_evaluation(
+            model, eval_set, device, group=info.ctrl_group if info.distributed else None,
+            pending_signal=monitor.pending, has_error=lambda: pending_err is not None)
+        if summary is None:
+            if err is not None:
+                logger.error(f"Evaluation error at step {step_now}: {err!r}")
+                if pending_err is None:
+                    pending_err = err
+            logger.info(f"Evaluation at step {step_now} abandoned (signal or error on a rank): no record")
+            boundary(final=final)  # the same signal / error columns: every rank stops here together
+            raise RuntimeError("an abandoned evaluation did not stop the run")
+        if info.is_main:
+            logger.info(evaluation.log_line(step_now, summary))
+            if metrics_f is not None:
+                metrics_f.write(json.dumps(evaluation.metrics_record(step_now, summary)) + "\n")
+                metrics_f.flush()
     emb_dim = margs.dim
     exit_code = 0
 
@@ -675,6 +709,8 @@ def train(args) -> int:
                 last_save_step = training_step
                 if args.no_async_checkpoint and st_ is not None:
                     prune_consumed()
+            if eval_set is not None and evaluation.should_evaluate(training_step, eval_every):
+                evaluate_at(training_step)
 
             if prof_range is not None and training_step == prof_range[0] and prof is None:
                 acts = [torch.profiler.ProfilerActivity.CPU]
@@ -795,6 +831,8 @@ def train(args) -> int:
         complete_pending()
         boundary.count = 0.0
         boundary(final=True)  # drains the loss log, last non-finite check, last signals
+        if eval_set is not None:
+            evaluate_at(training_step, final=True)
         if ckpt["engine"] is not None:
             ckpt["engine"].wait()
         log_digest(training_step)

@@ -268,6 +268,31 @@ def build_parser() -> argparse.ArgumentParser:
         "bf16 parameters only (--model-dtype bf16); not with --hip-graph / --compile",
     )
     parser.add_argument(
+        "--eval-every",
+        type=int,
+        default=0,
+        help="Held-out evaluation every N steps (at each step boundary with training_step %% N == 0 and "
+        "training_step > 0) and once more after the last step: a forward-only pass over a fixed set that "
+        "leaves the training state untouched bit for bit (0: off). Needs --eval-dataset unless "
+        "--synthetic-data",
+    )
+    parser.add_argument(
+        "--eval-sequences",
+        type=int,
+        default=32,
+        help="Size of the fixed evaluation set, in sequences of --sequence-length (default 32); a multiple "
+        "of --batch-size: the set runs as micro-batches of --batch-size sequences, micro-batch i on rank "
+        "i %% world size",
+    )
+    parser.add_argument(
+        "--eval-dataset",
+        type=str,
+        default="",
+        help="Parquet file or directory of the held-out set, read from its beginning with the same kind of "
+        "dataset as training (map-style, or the packing dataset under --iterable-dataset). Optional with "
+        "--synthetic-data: the set is then a synthetic stream whose seed the training stream never uses",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -296,4 +321,13 @@ def get_args(argv=None) -> argparse.Namespace:
     if args.stochastic_rounding and (args.hip_graph or args.compile):
         parser.error("--stochastic-rounding is not supported under whole-step graph replay "
                      "(--hip-graph / --compile): run the step eagerly")
+    if args.eval_every < 0:
+        parser.error(f"--eval-every must be >= 0, got {args.eval_every}")
+    if args.eval_every > 0:
+        if not args.eval_dataset and not args.synthetic_data:
+            parser.error("--eval-every needs a held-out set: give --eval-dataset (only --synthetic-data runs "
+                         "can do without one)")
+        if args.eval_sequences <= 0 or args.eval_sequences % args.batch_size:
+            parser.error(f"--eval-sequences ({args.eval_sequences}) must be a positive multiple of "
+                         f"--batch-size ({args.batch_size})")
     return args
