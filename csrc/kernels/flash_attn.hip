@@ -33,8 +33,6 @@
 #include "torch_utils.h"
 
 #include <cstdlib>
-#include <map>
-#include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -770,9 +768,9 @@ __global__ __launch_bounds__(256) void flash_bwd_pre_kernel(const bf16_t* __rest
   }
 }
 
-// DQ: 0 = dQ by fp32 atomics (default), 1 = no dQ stage (dK/dV only; a separate
-// deterministic dQ kernel follows), 2 = timing experiment: plain (racy) stores.
-template <class E, int D, int DQ = 0>
+// DQ: with dQ, by fp32 atomics (flash_bwd mode 0); else dK/dV only (a separate deterministic
+// dQ kernel runs before it).
+template <class E, int D, bool DQ>
 __global__ __launch_bounds__(256, 1) void flash_bwd_kernel(
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ qk, const bf16_t* __restrict__ qkv,
     const float* __restrict__ lse2, const float* __restrict__ delta, float* __restrict__ dq_acc,
@@ -811,9 +809,9 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_kernel(
   const float* delg = delta + ((long)b * Hq + h) * stat_stride(S);
 
   // K and V fragments of this wave's 32 keys -> VGPRs (the S = Q K^T and dP = dO V^T
-  // B operands, reused by every query slice); the in-kernel dQ stage (DQ != 1) also
+  // B operands, reused by every query slice); the in-kernel dQ stage (DQ) also
   // needs all 128 keys of K as an LDS image.
-  if constexpr (DQ != 1) {
+  if constexpr (DQ) {
 #pragma unroll
     for (int i = 0; i < BK * DCH / 256; ++i) {
       const int id = tid + i * 256, row = id / DCH, c = id % DCH;
@@ -930,7 +928,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_kernel(
           dv[db] = mfma32(pa[ss], tr_frag<E, D>(di, 16 * ss, db * 32, lane), dv[db]);
           dk[db] = mfma32(da[ss], tr_frag<E, D>(qi, 16 * ss, db * 32, lane), dk[db]);
         }
-      if constexpr (DQ != 1) {
+      if constexpr (DQ) {
         // dS -> LDS image [key][q] (4 x 8-B writes per lane) for the in-kernel dQ stage
         char* row = dsimg + (wave * 32 + l32) * 64;
 #pragma unroll
@@ -948,13 +946,13 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_kernel(
         slice(std::true_type{});
       else
         slice(std::false_type{});
-    } else if constexpr (DQ != 1) {
+    } else if constexpr (DQ) {
       char* row = dsimg + (wave * 32 + l32) * 64;
 #pragma unroll
       for (int g = 0; g < 4; ++g) *reinterpret_cast<uint2*>(row + (8 * g + 4 * hi) * 2) = make_uint2(0, 0);
     }
     // dQ[q, d] += scale * sum_keys dS[q, key] K[key, d]
-    if constexpr (DQ != 1) {
+    if constexpr (DQ) {
       __syncthreads();
       f32x16_t acc;
 #pragma unroll
@@ -971,11 +969,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int q = qb + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if constexpr (DQ == 0) {
-            if (q < S) atomicAdd(dq_acc + ((long)b * S + q) * ldo + (long)h * D + d, acc[r] * scale);
-          } else {
-            if (q < S) dq_acc[((long)b * S + q) * ldo + (long)h * D + d] = acc[r] * scale;
-          }
+          if (q < S) atomicAdd(dq_acc + ((long)b * S + q) * ldo + (long)h * D + d, acc[r] * scale);
         }
       }
     }
@@ -1005,7 +999,7 @@ __global__ __launch_bounds__(256, 1) void flash_bwd_kernel(
 
 // One 4-column unit (row t, columns col .. col + 3) of the GQA fold / RoPE backward into dqkv
 // (see flash_bwd_finalize_kernel): dQ from dq_acc (fp32) or rotated in place, dK / dV summed over
-// the G q-head partials in head order (the same order wherever it runs: bit-reproducible).
+// the G q-head partials in head order (bit-reproducible).
 template <class E>
 __device__ __forceinline__ void fin_unit(const float* __restrict__ dq_acc, const bf16_t* __restrict__ dk_part,
                                          const bf16_t* __restrict__ dv_part, bf16_t* __restrict__ dqkv, long t,
@@ -1041,7 +1035,6 @@ __device__ __forceinline__ void fin_unit(const float* __restrict__ dq_acc, const
     const float2 c = *reinterpret_cast<const float2*>(cos_t + pos * (D / 2) + fi);
     const float2 sn = *reinterpret_cast<const float2*>(sin_t + pos * (D / 2) + fi);
     const float a0 = v.x, b0 = v.y, a1 = v.z, b1 = v.w;
-    // explicit fmas: the in-kernel fold (gqa_fold_rows) rounds identically
     v.x = fmaf(a0, c.x, b0 * sn.x);
     v.y = fmaf(-a0, sn.x, b0 * c.x);
     v.z = fmaf(a1, c.y, b1 * sn.y);
@@ -1053,111 +1046,8 @@ __device__ __forceinline__ void fin_unit(const float* __restrict__ dq_acc, const
   *reinterpret_cast<uint2*>(dqkv + t * W + col) = o;
 }
 
-// In-kernel GQA fold of the deterministic dK/dV kernel (no finalize pass): every (b, kv head, key
-// tile) has G q-head blocks; each publishes its bf16 partial, fences, and bumps the tile's counter;
-// the block that brings it to G folds the tile's rows (dK / dV over the G partials, RoPE backward
-// of dK and of the group's dQ rows) and re-arms the counter for the next launch.
-struct GqaFold {
-  int* cnt;                // [B * Hkv * key tiles], zero between launches
-  bf16_t* dqkv;            // [T, (Hq + 2 Hkv) D]
-  const float* cos_t;      // RoPE tables or null
-  const float* sin_t;
-  int dbg;                 // timing experiments only: 1 no fold work, 2 no release fence
-  int q_done;              // dQ already rotated by the dQ kernel
-  int krot;                // no GQA (direct stores into dqkv): dK rotated back in the dK/dV kernel's row stores
-};
-
-// The fold of `rows` rows from t0 (one key tile of kv head kvh) by NT threads: 16-B units (8
-// columns), U units in flight per thread (loads first, then the sums / rotations / stores: the
-// per-unit load -> add -> store chains otherwise serialise on memory latency). Columns: the G
-// q-heads' dQ (RoPE only, rotated in place), then dK, then dV of the kv head. Sums in head order.
-template <class E, int D, int NT>
-__device__ __forceinline__ void gqa_fold_rows(const bf16_t* __restrict__ dk_part, const bf16_t* __restrict__ dv_part,
-                                              const GqaFold& f, long t0, int rows, int kvh, int G, int Hq, int Hkv,
-                                              int S, int tid) {
-  constexpr int U = 4, CU = D / 8;  // units per thread per pass, units per head row
-  const long W = (long)(Hq + 2 * Hkv) * D;
-  const int uq = f.cos_t != nullptr && !f.q_done ? G * CU : 0;
-  const int upr = uq + 2 * CU;
-  const int n = rows * upr;
-  for (int base = 0; base < n; base += NT * U) {
-    uint4 x[U][8];
-    int rr[U], u[U];
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      const int i = base + j * NT + tid;
-      rr[j] = i < n ? i / upr : -1;
-      u[j] = i < n ? i - rr[j] * upr : 0;
-      if (rr[j] < 0) continue;
-      const long t = t0 + rr[j];
-      if (u[j] < uq) {
-        x[j][0] = *reinterpret_cast<const uint4*>(f.dqkv + t * W + (long)kvh * G * D + 8 * u[j]);
-      } else {
-        const bool isk = u[j] < uq + CU;
-        const int c = 8 * (u[j] - uq - (isk ? 0 : CU));
-        const bf16_t* src = (isk ? dk_part : dv_part) + t * Hq * D + (long)kvh * G * D + c;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          if (r < G) x[j][r] = *reinterpret_cast<const uint4*>(src + r * D);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < U; ++j) {
-      if (rr[j] < 0) continue;
-      const long t = t0 + rr[j];
-      float v[8];
-      long col;
-      bool rot;
-      auto unpack_add = [&](const uint4& q, bool first) {
-        const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float lo = u16f<E>(w4[e]), hi = u16f<E>(w4[e] >> 16);
-          v[2 * e] = first ? lo : v[2 * e] + lo;
-          v[2 * e + 1] = first ? hi : v[2 * e + 1] + hi;
-        }
-      };
-      if (u[j] < uq) {
-        unpack_add(x[j][0], true);
-        col = (long)kvh * G * D + 8 * u[j];
-        rot = true;
-      } else {
-        const bool isk = u[j] < uq + CU;
-        const int c = 8 * (u[j] - uq - (isk ? 0 : CU));
-        // 0 + p0 + p1 + ... in head order, as flash_bwd_finalize_kernel
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-          if (r < G) unpack_add(x[j][r], false);
-        col = (isk ? (long)Hq * D : (long)(Hq + Hkv) * D) + (long)kvh * D + c;
-        rot = isk && f.cos_t != nullptr;
-      }
-      if (rot) {
-        const int fi = (int)(col % D) >> 1;
-        const long pos = t % S;
-        const float4 c4 = *reinterpret_cast<const float4*>(f.cos_t + pos * (D / 2) + fi);
-        const float4 s4 = *reinterpret_cast<const float4*>(f.sin_t + pos * (D / 2) + fi);
-        const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float a = v[2 * e], bb = v[2 * e + 1];
-          v[2 * e] = fmaf(a, cc[e], bb * ss[e]);
-          v[2 * e + 1] = fmaf(-a, ss[e], bb * cc[e]);
-        }
-      }
-      uint4 o;
-      o.x = pk2<E>(v[0], v[1]);
-      o.y = pk2<E>(v[2], v[3]);
-      o.z = pk2<E>(v[4], v[5]);
-      o.w = pk2<E>(v[6], v[7]);
-      *reinterpret_cast<uint4*>(f.dqkv + t * W + col) = o;
-    }
-  }
-}
-
 // ================================================================== backward dK/dV, slice pairs (deterministic)
-// flash_bwd_kernel<D, 1> with TWO independent 32-query slices per loop iteration: S / dP
+// flash_bwd_kernel<D, false> with TWO independent 32-query slices per loop iteration: S / dP
 // of both slices are issued back to back, and in the steady state (both slices fully
 // below the diagonal) the whole pair is one basic block, so the scheduler can run slice
 // A's softmax VALU and dV / dK MFMAs while slice B's S / dP MFMAs are in flight (at one
@@ -1167,11 +1057,9 @@ __device__ __forceinline__ void gqa_fold_rows(const bf16_t* __restrict__ dk_part
 // SPLIT = 2: two half-blocks take alternate slice pairs of the same keys and add their dK / dV
 // partials through LDS at the end (fixed order: bit-reproducible), halving the longest
 // (first) key block's sweep.
-// SD (self delta, the 3-kernel GQA backward): each slice's O rows come in by LDS-DMA beside its dO
-// rows and every wave forms the slice's delta = rowsum(dO * O) itself (the dQ kernel's arithmetic,
-// term for term: bitwise the same values), so this kernel runs FIRST and the dQ kernel after it
-// folds the GQA partials (no finalize pass).
-// DOC (flash_doc_bwd; unsplit, no SD): document-masked attention. Key j is seen by the queries
+// cos_t / sin_t (no GQA, dK / dV stored straight into dqkv): the RoPE tables when dK is rotated
+// back in the row stores, else null.
+// DOC (flash_doc_bwd; unsplit): document-masked attention. Key j is seen by the queries
 // j <= i < doc_end[j] (doc_end [B, S] int32, non-decreasing per sequence): the key tile's sweep
 // stops with the pair that holds row doc_end - 1 of the tile's last valid key, and slices that reach
 // doc_end of the wave's first key take the masked path with q >= doc_end[key] added -- for
@@ -1180,16 +1068,16 @@ __device__ __forceinline__ void gqa_fold_rows(const bf16_t* __restrict__ dk_part
 // statistics: neither 32 staged doc_start values per slice nor a register held across the sweep fit
 // the register budget (profiles/flash_doc.md). The values are clamped to [0, S] when loaded; they
 // only bound the sweep and feed compares.
-template <class E, int D, int NW = 4, int SPLIT = 1, bool SD = false, bool DOC = false>
+template <class E, int D, int NW = 4, int SPLIT = 1, bool DOC = false>
 __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SPLIT)) void flash_bwd_dkdv2_kernel(
     const bf16_t* __restrict__ dO, const bf16_t* __restrict__ qk, const bf16_t* __restrict__ qkv,
     const float* __restrict__ lse2, const float* __restrict__ delta, bf16_t* __restrict__ dk_part,
     bf16_t* __restrict__ dv_part, long ldkv, int B, int S, int Hq, int Hkv, float sl2, float scale, long ldqk_,
-    GqaFold fold, const bf16_t* __restrict__ O = nullptr, const int* __restrict__ doc_end = nullptr) {
-  static_assert(!DOC || (SPLIT == 1 && !SD), "the document mask is built into the unsplit kernel only");
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t, const int* __restrict__ doc_end = nullptr) {
+  static_assert(!DOC || SPLIT == 1, "the document mask is built into the unsplit kernel only");
   constexpr int BK = 32 * NW, BQ = 32, KS = D / 16, NDB = D / 32;
   constexpr int QIMG = BQ * D * 2;          // one Q or dO slice
-  constexpr int STO = (SD ? 3 : 2) * QIMG;  // lse[32] | delta[32] after Q | dO (| O)
+  constexpr int STO = 2 * QIMG;             // lse[32] | delta[32] after Q | dO
   constexpr int SLOT = STO + 256;           // one slice
   __shared__ __attribute__((aligned(16))) char pb0[2 * SLOT * SPLIT];  // pair buffer 0: slice A | slice B
   __shared__ __attribute__((aligned(16))) char pb1[2 * SLOT * SPLIT];  // pair buffer 1 (per half-block)
@@ -1213,7 +1101,6 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
   const bf16_t* dOg = dO + (long)b * S * ldo + (long)h * D;
   const float* lseg = lse2 + ((long)b * Hq + h) * stat_stride(S);
   const float* delg = delta + ((long)b * Hq + h) * stat_stride(S);
-  const bf16_t* Og = SD ? O + (long)b * S * ldo + (long)h * D : nullptr;
 
   typename FA<E>::v8 vf[KS], kf[KS];
   {
@@ -1260,9 +1147,8 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
           const long q = min(q0 + r, S - 1);
           glds16(Qg + q * ldqk + c * 8, sl + piece * 1024);
           glds16(dOg + q * ldo + c * 8, sl + QIMG + piece * 1024);
-          if constexpr (SD) glds16(Og + q * ldo + c * 8, sl + 2 * QIMG + piece * 1024);
         });
-        if (wave == half && lane < (SD ? 8 : 16)) {
+        if (wave == half && lane < 16) {
           // lanes 0-7: lse rows q0..q0+31, lanes 8-15: delta (rows padded to 32: in bounds)
           const float* src = lane < 8 ? lseg + q0 + 4 * lane : delg + q0 + 4 * (lane - 8);
           glds16(src, sl + STO);
@@ -1287,27 +1173,6 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     for (int ks = 0; ks < KS; ++ks) {
       sv = mfma32(ld_row<E, D>(qi, l32, 2 * ks + hi), kf[ks], sv);
       dpv = mfma32(ld_row<E, D>(di, l32, 2 * ks + hi), vf[ks], dpv);
-    }
-    if constexpr (SD) {
-      // delta of query row l32 of the slice, as flash_bwd_dq_kernel forms it: this lane's half of
-      // the dO . O dot product (columns 16 ks + 8 hi ..), plus lane ^ 32's; every wave writes the
-      // same 32 values into the slot's delta row, read back by its own fin (LDS is in order per wave)
-      const char* oi = sl + 2 * QIMG;
-      float acc = 0.f;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const auto dv = ld_row<E, D>(di, l32, 2 * ks + hi);
-        const auto ov = ld_row<E, D>(oi, l32, 2 * ks + hi);
-        float x[8], y[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = (float)dv[j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = (float)ov[j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc += x[j] * y[j];
-      }
-      const float dl = acc + __shfl_xor(acc, 32, 64);
-      if (hi == 0) reinterpret_cast<float*>(const_cast<char*>(sl) + STO)[BQ + l32] = dl;
     }
   };
   auto fin = [&](const char* sl, const int i, f32x16_t sv, f32x16_t dpv, auto MASKED)
@@ -1470,9 +1335,9 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
         const int so = r * (D * 2) + ((c ^ (r % CH)) << 4);
         const long off = ((long)b * S + k) * ldkv + (long)h * D + c * 8;
         uint4 kv = *reinterpret_cast<const uint4*>(stg + so);
-        if (fold.krot) {  // (uniform) RoPE backward of the 4 pairs of this dK chunk, as rope_bwd_ does it
-          const float4 c4 = *reinterpret_cast<const float4*>(fold.cos_t + (long)k * (D / 2) + c * 4);
-          const float4 s4 = *reinterpret_cast<const float4*>(fold.sin_t + (long)k * (D / 2) + c * 4);
+        if (cos_t != nullptr) {  // (uniform) RoPE backward of the 4 pairs of this dK chunk, as rope_bwd_ does it
+          const float4 c4 = *reinterpret_cast<const float4*>(cos_t + (long)k * (D / 2) + c * 4);
+          const float4 s4 = *reinterpret_cast<const float4*>(sin_t + (long)k * (D / 2) + c * 4);
           const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {-s4.x, -s4.y, -s4.z, -s4.w};
           float x[8], y[8];
           unpack8e<E>(kv, x);
@@ -1489,25 +1354,6 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
       }
     }
   }
-
-  if (fold.cnt != nullptr) {
-    // (SPLIT = 2: half-block 1 has exited; the barriers count the 64 * NW threads left)
-    __shared__ int s_last;
-    const int G = Hq / Hkv;
-    const int ci = (b * Hkv + kvh) * (int)(gridDim.x / per) + kt;
-    // release only (L2 write-back, no invalidate): an acquire here would drop every block's L2
-    // working set; only the folding block needs one
-    if (fold.dbg != 2) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // partial visible device-wide
-    __syncthreads();
-    if (tid == 0) s_last = atomicAdd(fold.cnt + ci, 1) == G - 1;
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // the other G - 1 partials
-    if (tid == 0) fold.cnt[ci] = 0;
-    if (fold.dbg != 1)
-      gqa_fold_rows<E, D, 64 * NW>(dk_part, dv_part, fold, (long)b * S + kb0, min(BK, S - kb0), kvh, G, Hq, Hkv, S,
-                                 tid);
-  }
 }
 
 // ================================================================== backward dQ (deterministic)
@@ -1517,13 +1363,15 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
 // the lane, so lse/delta are per-lane scalars), dQ^T += K^T dS^T (A = K^T through
 // transposed LDS reads, B = dS^T straight from the accumulators). Every dQ element
 // is produced by exactly one wave in a fixed order: no atomics, bit-reproducible.
-// Used with flash_bwd_kernel<D, 1> (dK/dV only) for --deterministic runs.
+// Runs before the dK/dV kernel (the slice-pair kernel or flash_bwd_kernel<D, false>) of the
+// deterministic backward.
 // SPLIT = 2 (small grids, see flash_bwd): as the forward's key split, two half-blocks sweep
 // the even / odd key tiles of the same queries and add their dQ partials through LDS (in a
 // fixed order: still bit-reproducible).
-// O != null: the kernel forms delta = rowsum(dO * O) itself (each lane pair already holds its
-// query's dO row) and publishes it for the dK/dV kernel that runs after it — the separate
-// flash_bwd_pre pass and its second read of dO are gone.
+// The kernel forms delta = rowsum(dO * O) itself (each lane pair already holds its query's dO
+// row) and writes it for the dK/dV kernel that runs after it: no flash_bwd_pre pass, no second
+// read of dO.
+// cos_t / sin_t: the RoPE tables when dQ is rotated back in the store, else null.
 // DOC (flash_doc_bwd; unsplit only): the document mask of flash_fwd_kernel<.., DOC> — the same
 // loop start, per-wave tile skip, masked-path condition and key < doc_start[qrow] element mask.
 template <class E, int D, int NW = 4, int SPLIT = 1, bool DOC = false>
@@ -1532,7 +1380,6 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     const float* __restrict__ lse2, float* __restrict__ delta, bf16_t* __restrict__ dqkv, int B,
     int S, int Hq, int Hkv, float sl2, float scale, long ldqk_, const bf16_t* __restrict__ O,
     const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-    const bf16_t* __restrict__ dk_part = nullptr, const bf16_t* __restrict__ dv_part = nullptr,
     const int* __restrict__ doc_start = nullptr) {
   static_assert(!DOC || SPLIT == 1, "the document mask is built into the unsplit kernel only");
   constexpr int BM = 32 * NW, BN = 64, KS = D / 16, NDB = D / 32;
@@ -1574,7 +1421,7 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
   }
   const float lq = lse2[((long)b * Hq + h) * stat_stride(S) + qr];
   float dlq;
-  if (O != nullptr) {  // uniform
+  {
     // delta of this lane's query: its half of the dO . O dot product, plus the other half
     // from lane ^ 32 (same query, the other 8 of every 16 columns); fp32 like flash_bwd_pre
     const bf16_t* Og = O + (long)b * S * ldo + (long)h * D + qr * ldo;
@@ -1591,8 +1438,6 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
     }
     dlq = acc + __shfl_xor(acc, 32, 64);
     if (half == 0 && hi == 0 && qrow < S) delta[((long)b * Hq + h) * stat_stride(S) + qrow] = dlq;
-  } else {
-    dlq = delta[((long)b * Hq + h) * stat_stride(S) + qr];
   }
 
   const int kend = min((qt + 1) * BM, S);
@@ -1745,63 +1590,15 @@ __global__ __launch_bounds__(64 * NW * SPLIT, SPLIT == 1 ? 4 / NW : 8 / (NW * SP
       return (i & 1) ? fmaf(-a0, sn, b0 * c) : fmaf(a0, c, b0 * sn);
     });
   }
-
-  if (dk_part != nullptr) {  // (uniform) the 3-kernel GQA backward: the dK/dV kernel ran first
-    // Fold of its per-q-head partials: this block takes key rows [qt BM, +BM) of kv head kvh and
-    // column slice gi (D / G columns) of dK and dV: the sum over the G q-heads in head order, dK
-    // rotated back (RoPE), as flash_bwd_finalize_kernel / gqa_fold_rows compute it (bitwise).
-    // (SPLIT = 2: half-block 1 has returned; the 64 NW threads of half 0 do it.)
-    const int G = Hq / Hkv, gi = h - kvh * G;
-    const int cps = D / G / 8;  // 16-B chunks per column slice
-    const int r0 = qt * BM, nr = min(BM, S - r0);
-    const long W = (long)(Hq + 2 * Hkv) * D;
-    const int n = nr * 2 * cps;
-    for (int i = tid; i < n; i += 64 * NW) {
-      const int row = i / (2 * cps), u = i - row * 2 * cps;
-      const bool isk = u < cps;
-      const int c = (gi * cps + (isk ? u : u - cps)) * 8;  // first column within the head
-      const long t = (long)b * S + r0 + row;
-      const bf16_t* src = (isk ? dk_part : dv_part) + t * Hq * D + (long)kvh * G * D + c;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = 0.f;
-      for (int g = 0; g < G; ++g) {
-        const uint4 q = *reinterpret_cast<const uint4*>(src + g * D);
-        const unsigned w4[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          v[2 * e] = v[2 * e] + u16f<E>(w4[e]);
-          v[2 * e + 1] = v[2 * e + 1] + u16f<E>(w4[e] >> 16);
-        }
-      }
-      if (isk && cos_t != nullptr) {
-        const long pos = r0 + row;
-        const float4 c4 = *reinterpret_cast<const float4*>(cos_t + pos * (D / 2) + (c >> 1));
-        const float4 s4 = *reinterpret_cast<const float4*>(sin_t + pos * (D / 2) + (c >> 1));
-        const float cc[4] = {c4.x, c4.y, c4.z, c4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float a = v[2 * e], bb = v[2 * e + 1];
-          v[2 * e] = fmaf(a, cc[e], bb * ss[e]);
-          v[2 * e + 1] = fmaf(-a, ss[e], bb * cc[e]);
-        }
-      }
-      uint4 o;
-      o.x = pk2<E>(v[0], v[1]);
-      o.y = pk2<E>(v[2], v[3]);
-      o.z = pk2<E>(v[4], v[5]);
-      o.w = pk2<E>(v[6], v[7]);
-      *reinterpret_cast<uint4*>(dqkv + t * W + (isk ? (long)Hq * D : (long)(Hq + Hkv) * D) + (long)kvh * D + c) = o;
-    }
-  }
 }
 
 // dqkv[:, q | k | v] = bf16(dQ), bf16(sum_G dK_part), bf16(sum_G dV_part).
 // cos_t != null: the Q and K columns are also rotated back (RoPE backward, reference
 // model.py:100-126 transposed: the interleaved pair (x0, x1) times cis(-theta)), so dqkv is the
 // gradient of the unrotated projection and no separate rope_bwd pass runs; dQ written by the
-// deterministic dQ kernel is rotated in place. The deterministic path folds inside the dK/dV kernel
-// (fin_unit from its last GQA block); this pass remains for the other backward variants.
+// deterministic dQ kernel is rotated in place, unless that kernel rotated it in its store (q_done).
+// This pass closes every backward that leaves per-q-head dK / dV partials: mode 0, and the
+// deterministic backward with GQA or with the one-slice dK/dV kernel.
 template <class E>
 __global__ __launch_bounds__(256) void flash_bwd_finalize_kernel(
     const float* __restrict__ dq_acc, const bf16_t* __restrict__ dk_part,
@@ -1845,27 +1642,15 @@ int g_dq_split = -1;
 int g_kv_split = -1;
 
 // Deterministic backward, dK/dV stage at head_dim 128: the slice-pair kernel (default) or the
-// one-slice flash_bwd_kernel<D, 1> (flash_set_dkdv2, for A/B).
+// one-slice flash_bwd_kernel<D, false> (flash_set_dkdv2, for A/B).
 bool g_dkdv2 = true;
 
-// GQA fold of the deterministic backward in the separate finalize pass (default) or inside the
-// dK/dV kernel by each key tile's last q-head block (flash_set_bwd_fold).
-// The in-kernel fold saves the launch but measured slower at the 8B layer (S = 2048, 32/8 heads,
-// RoPE): 296-307 us vs 175-193 us for the whole backward; its device-scope release fences and
-// counters alone cost ~16 us over the finalize variant without any fold work, and the folds run
-// as a 128-block tail behind the heaviest key tiles (profiles/r4_flash_gqa_fold_probe.log).
-bool g_bwd_fold = false;
-
-// GQA deterministic backward in 3 kernels (FT_FLASH_FOLD3=1 / flash_set_fold3(true)): the dK/dV
-// kernel first, forming delta itself from O (SD), then the dQ kernel, which also folds the GQA
-// partials (no finalize pass). Bitwise equal to the default 4-kernel order (dQ, dK/dV, finalize) but
-// slower at the 8B layer: 200.8 vs 165.7 us -- every wave of the dK/dV kernel forms its slices'
-// deltas on the critical path (88.6 -> 120.7 us), and the fold in the dQ kernel costs what the
-// finalize pass did (+11.6 vs 9.6 us) (profiles/r6/flash_fold3_ab.log). Off by default.
-bool g_fold3 = [] {
-  const char* e = std::getenv("FT_FLASH_FOLD3");
-  return e != nullptr && std::atoi(e) != 0;
-}();
+// With GQA the deterministic backward folds the per-q-head dK / dV partials in the finalize pass.
+// Two ways to save that launch were tried at the 8B layer and removed: the fold inside the dK/dV
+// kernel by each key tile's last block (296-307 us vs 175-193 us for the whole backward,
+// profiles/r4_flash_gqa_fold_probe.log), and three kernels with the fold at the end of the dQ
+// kernel (200.8 vs 165.7 us, the A/B log under profiles/r6/; profiles/flash_bwd_one_gqa_path.md
+// lists both logs).
 
 // No-GQA backward (GPT-2-sized presets): dQ rotated in the dQ kernel's store and dK in the dK/dV
 // kernel's, so no separate rope_bwd_ pass (3 kernels per layer); FT_FLASH_DIRECT_ROPE=0 /
@@ -1874,24 +1659,6 @@ bool g_direct_rope = [] {
   const char* e = std::getenv("FT_FLASH_DIRECT_ROPE");
   return e == nullptr || std::atoi(e) != 0;
 }();
-
-// The fold's per-tile arrival counters: one zeroed int32 buffer per device, grown on demand and
-// kept (each tile's last block re-arms its counter, so the buffer is zero between launches). One
-// backward in flight per device at a time (the training step's single compute stream). Under
-// stream capture a buffer that would have to be (re)allocated is not: the caller falls back to
-// the finalize pass.
-int* fold_counters(const c10::Device& dev, long n) {
-  static std::mutex mu;
-  static std::map<int, at::Tensor> bufs;
-  std::lock_guard<std::mutex> lock(mu);
-  at::Tensor& b = bufs[dev.index()];
-  if (!b.defined() || b.numel() < n) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(ft_stream(), &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
-    b = at::zeros({std::max(n, 4096L)}, at::TensorOptions().device(dev).dtype(at::kInt));
-  }
-  return b.data_ptr<int>();
-}
 
 // Waves (32 query or key rows each) per attention block: 2 when 4-wave blocks would leave
 // most of the 256 CUs idle (fewer than 512 blocks; head_dim 64 — the GPT-2-sized presets:
@@ -1978,24 +1745,23 @@ void launch_fwd(const FwdArgs& a, dim3 grid, bool split, bool pipe) {
 // Every decision of one backward, taken in plan_bwd (the only reader of the knobs above).
 struct BwdPlan {
   int mode;       // 0: dQ by fp32 atomics in the KV-major kernel (fastest); 1: deterministic -- the Q-major
-                  // dQ kernel + a dK/dV kernel without dQ (no atomics); 2: timing experiment only (racy dQ stores)
+                  // dQ kernel + a dK/dV kernel without dQ (no atomics)
   int nw;         // waves per block of the deterministic dQ and slice-pair dK/dV kernels
   bool doc;       // document mask (flash_doc_bwd)
-  bool dkdv2;     // dK/dV by the slice-pair kernel (else the one-slice flash_bwd_kernel<D, 1>)
+  bool dkdv2;     // dK/dV by the slice-pair kernel (else the one-slice flash_bwd_kernel<D, false>)
   bool kv_split;  // ... its split form
   bool dq_split;  // the dQ kernel's key split
   bool direct;    // no GQA: dK / dV stored into dqkv by the slice-pair kernel (no partials, no finalize pass)
-  int* fold;      // GQA fold inside the slice-pair kernel: its tile counters, else null
-  bool fold3;     // GQA in 3 kernels: dK/dV first (delta from O), then dQ + the fold
   bool krot;      // RoPE backward of dK in the slice-pair kernel's direct store
   bool q_rot;     // RoPE backward of dQ in the dQ kernel's store
 };
 
-BwdPlan plan_bwd(const c10::Device& dev, long S, long B, long Hq, long Hkv, long D, long mode, bool rope, bool doc) {
+// mode: 0 or 1 (checked by flash_bwd)
+BwdPlan plan_bwd(long S, long B, long Hq, long Hkv, long D, long mode, bool rope, bool doc) {
   BwdPlan p{};
   // the document mask is built into the unsplit deterministic kernels only
   p.doc = doc;
-  p.mode = doc || mode == 1 ? 1 : (mode == 0 ? 0 : 2);
+  p.mode = doc || mode == 1 ? 1 : 0;
   const bool det = p.mode == 1;
   p.nw = waves_per_block(S, B, Hq, D);
   const long tiles = (S + 32 * p.nw - 1) / (32 * p.nw);  // of the deterministic dK/dV and dQ kernels
@@ -2018,12 +1784,6 @@ BwdPlan plan_bwd(const c10::Device& dev, long S, long B, long Hq, long Hkv, long
   // (flash_set_direct_rope(false) restores that pass for Q and K, for A/B)
   p.krot = rope && p.direct && g_direct_rope;
   p.q_rot = rope && det && (!p.direct || p.krot);
-  const bool gqa = p.dkdv2 && !p.direct && !doc;
-  // the in-kernel fold holds at most 8 q-head partials per unit (uint4 x[U][8]): wider groups
-  // take the finalize pass
-  if (gqa && g_bwd_fold && Hq / Hkv <= 8) p.fold = fold_counters(dev, B * Hkv * tiles);
-  // 3-kernel GQA backward: a column slice of D / G columns per q-head block must be whole 16-B chunks
-  p.fold3 = gqa && g_fold3 && p.fold == nullptr && D % (8 * (Hq / Hkv)) == 0;
   return p;
 }
 
@@ -2032,22 +1792,20 @@ struct BwdArgs {
   const bf16_t *dout, *qk, *qkv, *out;
   const float* lse;
   float* delta;
-  float* dq_acc;                 // modes 0 / 2: the fp32 dQ accumulator, else null
+  float* dq_acc;                 // mode 0: the fp32 dQ accumulator, else null
   bf16_t* dqkv;
   bf16_t *dkp, *dvp;             // dK / dV of the kernels: the GQA partials [T, Hq D], or -- direct -- dqkv's columns
   long ldkv;                     // their row stride
   int B, S, Hq, Hkv;
   float sl2, scale;
   long ldqk;
-  GqaFold fold;
-  const float *dq_cos, *dq_sin;  // q_rot: the RoPE tables for the dQ kernel
-  const bf16_t *fkp, *fvp;       // fold3: the partials the dQ kernel folds
+  const float *cos_t, *sin_t;    // the RoPE tables, else null; BwdPlan says which launch rotates with them
   const int *doc_start, *doc_end;
 };
 
 inline dim3 det_grid(const BwdArgs& a, int nw) { return dim3(((a.S + 32 * nw - 1) / (32 * nw)) * a.B * a.Hq); }
 
-// delta = rowsum(dO * O) (modes 0 / 2; the deterministic kernels form it themselves)
+// delta = rowsum(dO * O) (mode 0; the deterministic dQ kernel forms it itself)
 template <class E, int D>
 void launch_pre(const BwdArgs& a) {
   const long rows = (long)a.B * a.S * a.Hq;
@@ -2055,8 +1813,8 @@ void launch_pre(const BwdArgs& a) {
                      a.dout, a.out, a.delta, a.B, a.S, a.Hq);
 }
 
-// the one-slice KV-major kernel: DQ = 0 / 2 with dQ (atomics / racy), 1 dK / dV only
-template <class E, int D, int DQ>
+// the one-slice KV-major kernel: DQ with dQ by atomics, else dK / dV only
+template <class E, int D, bool DQ>
 void launch_one_slice(const BwdArgs& a) {
   hipLaunchKernelGGL((flash_bwd_kernel<E, D, DQ>), dim3(((a.S + 127) / 128) * a.B * a.Hq), dim3(256), 0, ft_stream(),
                      a.dout, a.qk, a.qkv, a.lse, a.delta, a.dq_acc, a.dkp, a.dvp, a.B, a.S, a.Hq, a.Hkv, a.sl2,
@@ -2064,75 +1822,66 @@ void launch_one_slice(const BwdArgs& a) {
 }
 
 template <class E, int D, int NW, int SPLIT, bool DOC>
-void launch_dq_as(const BwdArgs& a) {
+void launch_dq_as(const BwdPlan& p, const BwdArgs& a) {
   hipLaunchKernelGGL((flash_bwd_dq_kernel<E, D, NW, SPLIT, DOC>), det_grid(a, NW), dim3(64 * NW * SPLIT), 0,
                      ft_stream(), a.dout, a.qk, a.qkv, a.lse, a.delta, a.dqkv, a.B, a.S, a.Hq, a.Hkv, a.sl2, a.scale,
-                     a.ldqk, a.out, a.dq_cos, a.dq_sin, a.fkp, a.fvp, a.doc_start);
+                     a.ldqk, a.out, p.q_rot ? a.cos_t : nullptr, p.q_rot ? a.sin_t : nullptr, a.doc_start);
 }
 
 // the deterministic dQ kernel
 template <class E, int D, int NW>
 void launch_dq(const BwdPlan& p, const BwdArgs& a) {
-  if (p.doc) launch_dq_as<E, D, NW, 1, true>(a);
-  else if (p.dq_split) launch_dq_as<E, D, NW, 2, false>(a);
-  else launch_dq_as<E, D, NW, 1, false>(a);
+  if (p.doc) launch_dq_as<E, D, NW, 1, true>(p, a);
+  else if (p.dq_split) launch_dq_as<E, D, NW, 2, false>(p, a);
+  else launch_dq_as<E, D, NW, 1, false>(p, a);
 }
 
-template <class E, int D, int NW, int SPLIT, bool SD, bool DOC>
-void launch_dkdv2_as(const BwdArgs& a) {
-  hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, D, NW, SPLIT, SD, DOC>), det_grid(a, NW), dim3(64 * NW * SPLIT), 0,
+template <class E, int D, int NW, int SPLIT, bool DOC>
+void launch_dkdv2_as(const BwdPlan& p, const BwdArgs& a) {
+  hipLaunchKernelGGL((flash_bwd_dkdv2_kernel<E, D, NW, SPLIT, DOC>), det_grid(a, NW), dim3(64 * NW * SPLIT), 0,
                      ft_stream(), a.dout, a.qk, a.qkv, a.lse, a.delta, a.dkp, a.dvp, a.ldkv, a.B, a.S, a.Hq, a.Hkv,
-                     a.sl2, a.scale, a.ldqk, a.fold, SD ? a.out : nullptr, a.doc_end);
+                     a.sl2, a.scale, a.ldqk, p.krot ? a.cos_t : nullptr, p.krot ? a.sin_t : nullptr, a.doc_end);
 }
 
-// the slice-pair dK/dV kernel (SD: it forms delta itself from O, fold3)
+// the slice-pair dK/dV kernel
 template <class E, int D, int NW>
 void launch_dkdv2(const BwdPlan& p, const BwdArgs& a) {
-  if (p.doc) return launch_dkdv2_as<E, D, NW, 1, false, true>(a);
+  if (p.doc) return launch_dkdv2_as<E, D, NW, 1, true>(p, a);
   if constexpr (D == 64 && NW == 4) {
     TORCH_INTERNAL_ASSERT(false, "flash_bwd: head_dim 64 with 4-wave blocks takes the one-slice dK/dV kernel");
   } else {
     if constexpr (D == 64) {  // the split form, see plan_bwd
-      if (p.kv_split) return p.fold3 ? launch_dkdv2_as<E, D, NW, 2, true, false>(a)
-                                     : launch_dkdv2_as<E, D, NW, 2, false, false>(a);
+      if (p.kv_split) return launch_dkdv2_as<E, D, NW, 2, false>(p, a);
     }
-    p.fold3 ? launch_dkdv2_as<E, D, NW, 1, true, false>(a) : launch_dkdv2_as<E, D, NW, 1, false, false>(a);
+    launch_dkdv2_as<E, D, NW, 1, false>(p, a);
   }
 }
 
-// the deterministic backward's dQ and dK/dV kernels
+// the deterministic backward's kernels: dQ first (it forms delta, no flash_bwd_pre pass), then dK/dV
 template <class E, int D, int NW>
 void launch_det(const BwdPlan& p, const BwdArgs& a) {
-  if (!p.dkdv2) {
-    launch_dq<E, D, NW>(p, a);
-    launch_one_slice<E, D, 1>(a);
-  } else if (p.fold3) {  // dK/dV first (it forms delta itself), dQ after it (folds the partials it wrote)
-    launch_dkdv2<E, D, NW>(p, a);
-    launch_dq<E, D, NW>(p, a);
-  } else {  // dQ first: it forms delta for the dK/dV kernel (no flash_bwd_pre pass)
-    launch_dq<E, D, NW>(p, a);
-    launch_dkdv2<E, D, NW>(p, a);
-  }
+  launch_dq<E, D, NW>(p, a);
+  if (p.dkdv2) launch_dkdv2<E, D, NW>(p, a);
+  else launch_one_slice<E, D, false>(a);
 }
 
 // All launches of one backward.
 template <class E, int D>
 void launch_bwd(const BwdPlan& p, const BwdArgs& a) {
-  if (p.mode != 1) {
+  if (p.mode == 0) {
     launch_pre<E, D>(a);
-    p.mode == 0 ? launch_one_slice<E, D, 0>(a) : launch_one_slice<E, D, 2>(a);
+    launch_one_slice<E, D, true>(a);
   } else if (D == 64 && p.nw == 2) {
     launch_det<E, 64, 2>(p, a);
   } else {
     launch_det<E, D, 4>(p, a);
   }
-  // folded already: no GQA | by the dK/dV kernel's last block per tile | by the dQ kernel
-  if (p.direct || p.fold != nullptr || p.fold3) return;
+  // no GQA: the slice-pair kernel stored dK / dV into dqkv, no partials to fold
+  if (p.direct) return;
   const long vec = (long)a.B * a.S * ((a.Hq + 2 * a.Hkv) * D / 4);
   const int fin_blocks = (int)std::max(1L, std::min((vec + 255) / 256, 4096L));
   hipLaunchKernelGGL((flash_bwd_finalize_kernel<E>), dim3(fin_blocks), dim3(256), 0, ft_stream(), a.dq_acc, a.dkp,
-                     a.dvp, a.dqkv, (long)a.B * a.S, a.Hq, a.Hkv, D, a.fold.cos_t, a.fold.sin_t, a.S,
-                     p.q_rot ? 1 : 0);
+                     a.dvp, a.dqkv, (long)a.B * a.S, a.Hq, a.Hkv, D, a.cos_t, a.sin_t, a.S, p.q_rot ? 1 : 0);
 }
 
 }  // namespace
@@ -2181,11 +1930,11 @@ static at::Tensor run_bwd(const at::Tensor& dout, const at::Tensor& qk, const at
   auto dqkv = at::empty({T, (Hq + 2 * Hkv) * D}, qk.options());
   if (T == 0) return dqkv;
   const bool rope = cos_t != nullptr;
-  const BwdPlan p = plan_bwd(qk.device(), S, B, Hq, Hkv, D, mode, rope, doc_start != nullptr);
+  const BwdPlan p = plan_bwd(S, B, Hq, Hkv, D, mode, rope, doc_start != nullptr);
   auto f32 = qk.options().dtype(at::kFloat);
   auto delta = at::empty({B, Hq, (long)stat_stride(S)}, f32);
   at::Tensor dq_acc, dk_part, dv_part;
-  if (p.mode != 1) dq_acc = p.mode == 2 ? at::empty({T, Hq * D}, f32) : at::zeros({T, Hq * D}, f32);
+  if (p.mode == 0) dq_acc = at::zeros({T, Hq * D}, f32);
   if (!p.direct) {
     dk_part = at::empty({T, Hq * D}, qk.options());
     dv_part = at::empty({T, Hq * D}, qk.options());
@@ -2193,14 +1942,11 @@ static at::Tensor run_bwd(const at::Tensor& dout, const at::Tensor& qk, const at
   bf16_t* const dq = mptr<bf16_t>(dqkv);
   bf16_t* const dkp = p.direct ? dq + (long)Hq * D : mptr<bf16_t>(dk_part);
   bf16_t* const dvp = p.direct ? dq + (long)(Hq + Hkv) * D : mptr<bf16_t>(dv_part);
-  const float* const cs = rope ? cptr<float>(*cos_t) : nullptr;
-  const float* const sn = rope ? cptr<float>(*sin_t) : nullptr;
   const BwdArgs a{cptr<bf16_t>(dout), cptr<bf16_t>(qk), cptr<bf16_t>(qkv), cptr<bf16_t>(out), cptr<float>(lse),
-                  mptr<float>(delta), p.mode != 1 ? mptr<float>(dq_acc) : nullptr, dq, dkp, dvp,
+                  mptr<float>(delta), p.mode == 0 ? mptr<float>(dq_acc) : nullptr, dq, dkp, dvp,
                   p.direct ? (long)(Hq + 2 * Hkv) * D : (long)Hq * D, B, (int)S, (int)Hq, (int)Hkv,
                   LOG2E_F / std::sqrt((float)D), 1.f / std::sqrt((float)D), qk.size(-1),
-                  GqaFold{p.fold, dq, cs, sn, 0, p.q_rot ? 1 : 0, p.krot ? 1 : 0}, p.q_rot ? cs : nullptr,
-                  p.q_rot ? sn : nullptr, p.fold3 ? dkp : nullptr, p.fold3 ? dvp : nullptr,
+                  rope ? cptr<float>(*cos_t) : nullptr, rope ? cptr<float>(*sin_t) : nullptr,
                   p.doc ? cptr<int>(*doc_start) : nullptr, p.doc ? cptr<int>(*doc_end) : nullptr};
   FT_DISPATCH_E16(qk.scalar_type(), {
     if (D == 128) launch_bwd<E, 128>(p, a); else launch_bwd<E, 64>(p, a);
@@ -2227,6 +1973,7 @@ at::Tensor flash_bwd(const at::Tensor& dout, const at::Tensor& qk, const at::Ten
                      const at::Tensor& out, const at::Tensor& lse, int64_t S, int64_t Hq,
                      int64_t Hkv, int64_t D, int64_t mode, const std::optional<at::Tensor>& cos_t,
                      const std::optional<at::Tensor>& sin_t) {
+  TORCH_CHECK(mode == 0 || mode == 1, "flash_bwd: mode must be 0 (dQ by atomics) or 1 (deterministic), got ", mode);
   check_inputs(qk, qkv, S, Hq, Hkv, D);
   check_bwd("flash_bwd", dout, out, lse, qk, S, Hq, D);
   const bool rope = check_rope("flash_bwd", cos_t, sin_t, S, D);
@@ -2263,7 +2010,7 @@ at::Tensor flash_doc_bwd(const at::Tensor& dout, const at::Tensor& qk, const at:
                  rope ? &*sin_t : nullptr);
 }
 
-// Same-process A/B switch: slice-pair dK/dV kernel vs flash_bwd_kernel<D, 1>.
+// Same-process A/B switch: slice-pair dK/dV kernel vs flash_bwd_kernel<D, false>.
 void flash_set_dkdv2(bool on) { g_dkdv2 = on; }
 // Same-process A/B switch of the forward key split: -1 auto, 0 off, 1 on.
 void flash_set_fwd_split(int64_t v) { g_fwd_split = (int)v; }
@@ -2280,9 +2027,7 @@ void flash_set_fwd_prof(const std::optional<at::Tensor>& buf) {
   }
 }
 void flash_set_kv_split(int64_t v) { g_kv_split = (int)v; }
-void flash_set_bwd_fold(bool on) { g_bwd_fold = on; }
 void flash_set_direct_rope(bool on) { g_direct_rope = on; }
-void flash_set_fold3(bool on) { g_fold3 = on; }
 
 TORCH_LIBRARY_FRAGMENT(ftamd, m) {
   m.def("flash_set_dkdv2(bool on) -> ()", &flash_set_dkdv2);
@@ -2291,9 +2036,7 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
   m.def("flash_set_fwd_pipe(int v) -> ()", &flash_set_fwd_pipe);
   m.def("flash_set_fwd_prof(Tensor? buf) -> ()", &flash_set_fwd_prof);
   m.def("flash_set_kv_split(int v) -> ()", &flash_set_kv_split);
-  m.def("flash_set_bwd_fold(bool on) -> ()", &flash_set_bwd_fold);
   m.def("flash_set_direct_rope(bool on) -> ()", &flash_set_direct_rope);
-  m.def("flash_set_fold3(bool on) -> ()", &flash_set_fold3);
   m.def("flash_fwd(Tensor qk, Tensor qkv, int S, int Hq, int Hkv, int D) -> (Tensor, Tensor)",
         &flash_fwd);
   m.def(

@@ -27,6 +27,8 @@ from .._native import kernels, native
 # as fast as 0 = dQ accumulated with fp32 atomics in the KV-major kernel (Llama-3-8B
 # layer shape: profiles/r1_flash_kernels.md).
 _BWD_MODE = int(os.environ.get("FT_FLASH_BWD_MODE", "1"))
+if _BWD_MODE not in (0, 1):
+    raise ValueError(f"FT_FLASH_BWD_MODE must be 0 (dQ by atomics) or 1 (deterministic), got {_BWD_MODE}")
 
 
 def set_deterministic(flag: bool) -> None:

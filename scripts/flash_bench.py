@@ -47,7 +47,7 @@ if hasattr(K, "flash_set_fwd_pipe"):  # software-pipelined forward off / on (def
         tf = t(lambda: K.flash_fwd(qk, qkv, S, Hq, Hkv, D))
         print(f"fwd {name:26s} {tf:7.1f} us  {2 * unit / tf / 1e6:6.0f} TF/s")
     K.flash_set_fwd_pipe(1)
-for mode, name in ((0, "bwd atomics"), (1, "bwd deterministic"), (2, "bwd no-atomic (racy, timing only)")):
+for mode, name in ((0, "bwd atomics"), (1, "bwd deterministic")):
     tb = t(lambda: K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, mode))
     print(f"{name:34s} {tb:7.1f} us  {5 * unit / tb / 1e6:6.0f} TF/s (5-matmul count)")
 if hasattr(K, "flash_set_dkdv2"):

@@ -255,13 +255,14 @@ def test_flash_bwd_with_rope_backward(B, S, Hq, Hkv, D, mode):
         assert torch.equal(got, K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, mode, cos, sin))
 
 
-@pytest.mark.parametrize("B,S,Hq,Hkv,D,rope", [(1, 2048, 32, 8, 128, True), (2, 320, 8, 2, 128, False),
-                                               (1, 1000, 4, 1, 128, True), (2, 512, 8, 2, 64, True),
-                                               (1, 100, 6, 2, 64, False), (1, 512, 16, 1, 128, True)])
-def test_flash_bwd_in_kernel_gqa_fold(B, S, Hq, Hkv, D, rope):
-    """Deterministic backward, opt-in variant (flash_set_bwd_fold): the GQA fold (+ RoPE backward)
-    done by the last q-head block of each key tile inside the dK/dV kernel == the finalize pass, bit
-    for bit (same head order), and stays so over repeated launches (the counters re-arm)."""
+@pytest.mark.parametrize("B,S,Hq,Hkv,D,rope", [(2, 320, 8, 2, 128, False), (1, 1000, 4, 1, 128, True),
+                                               (2, 512, 8, 2, 64, True), (1, 100, 6, 2, 64, False),
+                                               (1, 512, 16, 1, 128, True), (1, 777, 16, 2, 128, True)])
+def test_flash_bwd_gqa_finalize_shapes(B, S, Hq, Hkv, D, rope):
+    """Deterministic GQA backward (dQ kernel, dK/dV kernel, finalize pass) at odd shapes: ragged
+    sequence ends, groups of 3 / 4 / 8 / 16 q-heads per KV head, both head sizes, more than one
+    batch row. Without tables against the fp32 reference; with tables against flash_bwd + rope_bwd_
+    (within one bf16 rounding); bit-reproducible over repeated launches."""
     from fault_tolerant_llm_training_amd._native import kernels
     from fault_tolerant_llm_training_amd.models.llama import rope_tables
 
@@ -271,17 +272,30 @@ def test_flash_bwd_in_kernel_gqa_fold(B, S, Hq, Hkv, D, rope):
     qkv = torch.randn(T, (Hq + 2 * Hkv) * D, device="cuda").bfloat16()
     qk = torch.randn(T, (Hq + Hkv) * D, device="cuda").bfloat16()
     do = torch.randn(T, Hq * D, device="cuda").bfloat16()
-    cs = tuple(t.cuda() for t in rope_tables(D, S, 500000.0)) if rope else (None, None)
+    cos, sin = (t.cuda() for t in rope_tables(D, S, 500000.0))
     o, lse = K.flash_fwd(qk, qkv, S, Hq, Hkv, D)
-    try:
-        K.flash_set_bwd_fold(False)
-        ref = K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1, *cs)
-        K.flash_set_bwd_fold(True)
-        outs = [K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1, *cs) for _ in range(3)]
-    finally:
-        K.flash_set_bwd_fold(False)
-    for g in outs:
-        assert torch.equal(g, ref)  # (G = 16 > 8: the fold is skipped, the finalize pass runs)
+    cols = ((0, Hq * D), (Hq * D, (Hq + Hkv) * D), ((Hq + Hkv) * D, (Hq + 2 * Hkv) * D))
+    # (a) no tables: the fp32 autograd gradient
+    plain = K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1)
+    q = qk[:, : Hq * D].float().view(B, S, Hq, D).requires_grad_(True)
+    k = qk[:, Hq * D :].float().view(B, S, Hkv, D).requires_grad_(True)
+    v = qkv[:, (Hq + Hkv) * D :].float().view(B, S, Hkv, D).requires_grad_(True)
+    grads = torch.autograd.grad(ref_attn(q, k, v), (q, k, v), do.float().view(B, S, Hq, D))
+    for (lo, hi), g in zip(cols, grads):
+        assert rel(plain[:, lo:hi], g.reshape(T, -1)) < 2e-2, (lo, hi)
+    # (b) tables: flash_bwd without them, then rope_bwd_
+    ref = plain.clone()
+    K.rope_bwd_(ref, cos, sin, S, Hq, Hkv, D)
+    rot = K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1, cos, sin)
+    for lo, hi in cols:
+        assert rel(rot[:, lo:hi], ref[:, lo:hi]) < 4e-3, (lo, hi)
+    # (c) three consecutive launches
+    cs = (cos, sin) if rope else (None, None)
+    outs = [K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1, *cs) for _ in range(3)]
+    assert torch.equal(outs[0], rot if rope else plain)
+    assert torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0])
+    with pytest.raises(RuntimeError, match="mode must be 0"):
+        K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 2)
 
 
 def test_flash_fwd_timing_probe():
@@ -343,30 +357,3 @@ def test_no_gqa_rope_in_kernel_matches_the_separate_pass(S, H, D):
         K.flash_set_direct_rope(True)
     assert rel(got[:, : H * D], sep[:, : H * D]) < 4e-3
     assert torch.equal(got[:, H * D:], sep[:, H * D:])
-
-
-@pytest.mark.parametrize("B,S,Hq,Hkv,D,rope", [(1, 2048, 32, 8, 128, True), (2, 320, 8, 2, 128, False),
-                                               (1, 1000, 4, 1, 128, True), (2, 512, 8, 2, 64, True),
-                                               (1, 100, 6, 2, 64, False), (1, 777, 16, 2, 128, True)])
-def test_gqa_backward_in_three_kernels_equals_four(B, S, Hq, Hkv, D, rope):
-    """GQA deterministic backward in 3 kernels (flash_set_fold3(True): dK/dV first forming delta from
-    O, then dQ folding the per-q-head partials) == the default 4-kernel order (dQ, dK/dV, finalize),
-    bit for bit: delta, the fold order and the RoPE arithmetic are term-for-term the same."""
-    from fault_tolerant_llm_training_amd._native import kernels
-    from fault_tolerant_llm_training_amd.models.llama import rope_tables
-
-    K = kernels()
-    torch.manual_seed(S + Hq)
-    T = B * S
-    qkv = torch.randn(T, (Hq + 2 * Hkv) * D, device="cuda").bfloat16()
-    qk = torch.randn(T, (Hq + Hkv) * D, device="cuda").bfloat16()
-    do = torch.randn(T, Hq * D, device="cuda").bfloat16()
-    cs = tuple(t.cuda() for t in rope_tables(D, S, 500000.0)) if rope else (None, None)
-    o, lse = K.flash_fwd(qk, qkv, S, Hq, Hkv, D)
-    four = K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1, *cs)
-    try:
-        K.flash_set_fold3(True)
-        three = K.flash_bwd(do, qk, qkv, o, lse, S, Hq, Hkv, D, 1, *cs)
-    finally:
-        K.flash_set_fold3(False)
-    assert torch.equal(three, four), (three.float() - four.float()).abs().max().item()
