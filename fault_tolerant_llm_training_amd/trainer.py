@@ -645,6 +645,32 @@ def train(args) -> int:
             if metrics_f is not None:
                 metrics_f.write(json.dumps(evaluation.metrics_record(step_now, summary)) + "\n")
                 metrics_f.flush()
+
+    stats_every = int(getattr(args, "tensor_stats_every", 0) or 0)
+    tstats = None
+    first_boundary = training_step  # no backward has run in this process at its first boundary
+    last_backward = None  # the training step whose backward the gradient buffer holds
+    if stats_every > 0:
+        from .utils import tensor_stats
+
+        tstats = tensor_stats.StateStats(model, optimizer, info.rank, W,
+                                         group=info.ctrl_group if info.distributed else None)
+        logger.info(f"Tensor stats: every {stats_every} steps -- sumsq / absmax / non-finite / zeros of every "
+                    f"parameter's weights, gradient, exp_avg and exp_avg_sq ({len(tstats.names)} parameters)")
+
+    def tensor_stats_at(step_now: int) -> None:
+        """--tensor-stats-every: one record at step boundary ``step_now`` (every rank calls it, after the
+        boundary's vote, a periodic save and an evaluation): the gradient buffer as the backward of step
+        ``step_now - 1`` left it (unclipped), parameters and moments after that step's update. Read-only
+        passes on the compute stream, behind the optimizer's stream and ahead of the next backward."""
+        complete_pending()  # graph mode: the parameters and moments of this boundary
+        rec = tstats.collect()
+        if rec is not None:
+            logger.info(tensor_stats.log_line(step_now, rec))
+            if metrics_f is not None:
+                metrics_f.write(json.dumps(tensor_stats.metrics_record(step_now, rec)) + "\n")
+                metrics_f.flush()
+
     emb_dim = margs.dim
     exit_code = 0
 
@@ -711,6 +737,8 @@ def train(args) -> int:
                     prune_consumed()
             if eval_set is not None and evaluation.should_evaluate(training_step, eval_every):
                 evaluate_at(training_step)
+            if tstats is not None and tensor_stats.should_record(training_step, stats_every, first_boundary):
+                tensor_stats_at(training_step)
 
             if prof_range is not None and training_step == prof_range[0] and prof is None:
                 acts = [torch.profiler.ProfilerActivity.CPU]
@@ -806,6 +834,7 @@ def train(args) -> int:
                     raise _FatalStepError(f"could not complete step {training_step} after {e!r}: {e2!r}") from e2
                 lr_now = optimizer.param_groups[0]["lr"]
             steps_window += 1
+            last_backward = training_step
 
             if pending_err is None and (training_step == 1 or training_step % args.logging_frequency == 0):
                 extra = {"lr": f"{lr_now:.3e}"}
@@ -833,6 +862,8 @@ def train(args) -> int:
         boundary(final=True)  # drains the loss log, last non-finite check, last signals
         if eval_set is not None:
             evaluate_at(training_step, final=True)
+        if tstats is not None and tensor_stats.should_record(training_step, stats_every, first_boundary):
+            tensor_stats_at(training_step)
         if ckpt["engine"] is not None:
             ckpt["engine"].wait()
         log_digest(training_step)
@@ -846,6 +877,15 @@ def train(args) -> int:
         except Exception as we:  # noqa: BLE001
             logger.error(f"previous checkpoint write failed: {we!r}")
         step_now = training_step
+        if tstats is not None and isinstance(e, NonFiniteGradError) and last_backward is not None:
+            # which tensors hold the NaN / Inf: the gradient buffer as it stands (every rank: ZeRO-1
+            # combines the shards), after the rollback and before the save; read-only
+            try:
+                rec = tstats.collect(("grads",))
+                if rec is not None:
+                    logger.error(tensor_stats.nonfinite_line(last_backward, rec))
+            except Exception as te:  # noqa: BLE001 - the diagnosis never costs the checkpoint
+                logger.error(f"Tensor stats of the non-finite gradient failed: {te!r}")
 
         def _save():
             with monitor.blocked():

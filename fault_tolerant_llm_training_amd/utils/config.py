@@ -293,6 +293,17 @@ def build_parser() -> argparse.ArgumentParser:
         "--synthetic-data: the set is then a synthetic stream whose seed the training stream never uses",
     )
     parser.add_argument(
+        "--tensor-stats-every",
+        type=int,
+        default=0,
+        help="Per-parameter statistics every N steps (at each step boundary with training_step %% N == 0 and "
+        "training_step > 0, the final one included; never at the first boundary of a process, where no "
+        "backward has run): sum of squares, absmax, non-finite count and zero count of every parameter's "
+        "weights, gradient (of the step just taken, unclipped), exp_avg and exp_avg_sq, one read-only pass per "
+        "flat buffer; one log line, and one JSON line in --metrics-file. A non-finite stop then also names "
+        "the parameters whose gradient holds NaN / Inf (0: off)",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -323,6 +334,8 @@ def get_args(argv=None) -> argparse.Namespace:
                      "(--hip-graph / --compile): run the step eagerly")
     if args.eval_every < 0:
         parser.error(f"--eval-every must be >= 0, got {args.eval_every}")
+    if args.tensor_stats_every < 0:
+        parser.error(f"--tensor-stats-every must be >= 0, got {args.tensor_stats_every}")
     if args.eval_every > 0:
         if not args.eval_dataset and not args.synthetic_data:
             parser.error("--eval-every needs a held-out set: give --eval-dataset (only --synthetic-data runs "
