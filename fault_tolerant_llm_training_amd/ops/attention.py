@@ -217,6 +217,8 @@ def rope_attention(qkv, cos, sin, seq_len, hq, hkv, d, keep: Optional[AttentionK
 _QKV_ROPE = True
 # model dim from which the fused projection wins (see _qkv_rope_ok; FT_QKV_ROPE_MIN_K: A/B)
 _QKV_ROPE_MIN_K = int(os.environ.get("FT_QKV_ROPE_MIN_K", "2048"))
+# output tiles its grid needs: half the chip (the kernel takes no K split; see _qkv_rope_ok)
+_QKV_ROPE_MIN_TILES = 128
 
 
 def set_qkv_rope(on: bool) -> None:
@@ -235,7 +237,7 @@ def _qkv_rope_ok(x2: torch.Tensor, w: torch.Tensor, d: int) -> bool:
     if d % 8 or K < _QKV_ROPE_MIN_K or not Fx.w4_route(T, N, K, False, False, x2, w):
         return False
     nj = kernels().gemm_w4_pick(T, N)
-    return nj > 0 and (T // 256) * (N // (32 * nj)) >= Fx._W4_MIN_TILES
+    return nj > 0 and (T // 256) * (N // (32 * nj)) >= _QKV_ROPE_MIN_TILES
 
 
 class QKVRopeFn(torch.autograd.Function):

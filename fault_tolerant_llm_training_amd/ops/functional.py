@@ -40,12 +40,15 @@ IGNORE_INDEX = -100
 # GEMM routing. Every product of the step runs on the hand-written gfx950 "w4" kernel
 # (csrc/kernels/gemm_w4.h) on its operands as stored -- forward x W^T (K-contiguous), dX = dY W
 # (k-major W), dW = dY^T X (k-major dY and X, into the flat gradient buffer with the gradient-norm
-# partials in the epilogue). The GPT-2-sized products (18-96 tiles at one sequence per GPU) take a
-# deterministic K split (the dW layout too since round 6) and, for the LM-head dW at V = 50304, a
-# tail tile (M % 256). Per-product plans and measurements: profiles/r6/gpt2_gemm_probe_*.log,
-# profiles/r5_w4_split_bench.log; the routing table per preset: tests/test_routing_cpu.py.
-# set_w4_small(False) (FT_W4_SMALL=0) restores the round-5 routing of the small products to
-# hipBLASLt (A/B); the 128 x 128-tile kernel (gemm_s.hip, set_gemm_s) is opt-in.
+# partials in the epilogue). The kernel's planner (pick_plan, gemm_w4.hip) picks the tile width and
+# a deterministic K split per shape: the GPT-2-sized products (18-96 tiles at one sequence per GPU)
+# and the deep-reduction dX products run split, the LM-head dW at V = 50304 with a tail tile
+# (M % 256). Per-product plans and measurements: profiles/r6/gpt2_gemm_probe_*.log,
+# profiles/r5_w4_split_bench.log. fp32 models run the same products on the fp32 MFMA kernel
+# (gemm_f32.hip); hipBLASLt takes what neither hand-written kernel does.
+# One chooser per product (fwd_kernel, dx_kernel, dw_kernel) holds that order -- w4, else fp32
+# MFMA, else hipBLASLt -- and the stored-layout conditions; mm_fwd, mm_dx and _dw_into switch on
+# its result, and ops/routing.py prints it per preset (pinned by tests/test_routing_cpu.py).
 # ---------------------------------------------------------------------------------------------
 # FT_GEMM_BLAS=1: every GEMM on hipBLASLt (and the separate RoPE / SwiGLU kernels): the plain
 # reference path of convergence comparisons (scripts/gpu_convergence.sh)
@@ -70,18 +73,12 @@ def f32_route(M: int, N: int, K: int, a_t: bool, b_t: bool, *ts) -> bool:
         return False
     return K % 32 == 0 and K > 0 and (not a_t or M % 4 == 0) and (not b_t or N % 4 == 0) and all(
         t.shape[-1] % 4 == 0 for t in ts)
-# Workgroups (output tiles x K slices) a product needs before it goes to the w4 kernel: half the
-# chip. (Tests lower it to drive small shapes through the same paths.)
-_W4_MIN_TILES = 128
-_W4_SHORT_K = 1024
-_W4_DEEP_K = 4096
-_W4_SMALL = os.environ.get("FT_W4_SMALL", "1") != "0"  # round 6: the GPT-2-sized products on w4 too
-_W4_SMALL_WGS = 16  # ... from this many workgroups (the GPT-2-small wo dW: 18 tiles x 3 slices)
 
 
-def set_w4_small(on: bool) -> None:
-    global _W4_SMALL
-    _W4_SMALL = bool(on)
+# Workgroups (output tiles x K slices) a product needs before it goes to the w4 kernel (the
+# smallest product of the presets, the GPT-2-small wo dW, has 18 tiles x 3 slices). Tests lower it
+# to drive small shapes through the same paths.
+_W4_MIN_WGS = 16
 
 
 def set_w4_fwd(on: bool) -> None:
@@ -120,142 +117,91 @@ def w4_route(M: int, N: int, K: int, a_t: bool, b_t: bool, *ts) -> bool:
         return False
     if (M % 256 and not (a_t and M % 8 == 0)) or K % 128 or K < 128:  # K-tiles of 64 in pairs
         return False
-    nj, splits = _w4_plan(M, N, K, a_t, b_t)
-    if nj == 0:
-        return False
-    wgs = -(-M // 256) * (N // (32 * nj)) * splits
-    if _W4_SMALL:
-        return wgs >= min(_W4_MIN_TILES, _W4_SMALL_WGS)
-    if M % 256:
-        return False
-    if a_t:  # dW (round 5: never split)
-        return wgs >= _W4_MIN_TILES
-    # forward / dX below a full round (GPT-2 sizes, profiles/r5_gpt2_gemm_probe.log): short
-    # reductions (K <= 1024: wo forward / dX on 48-64 tiles, 1.15-1.39x hipBLASLt) and deep
-    # split ones (K >= 4096: w1|w3 dX, 1.14-1.25x) win; the 2048-3072-deep ones in between lose
-    # (w2 forward 0.82-0.88x, -medium qkv dX 0.94x)
-    return wgs >= 256 or (K <= _W4_SHORT_K and wgs >= 32) or (K >= _W4_DEEP_K and wgs >= _W4_MIN_TILES)
+    return _w4_wgs(M, N, K, a_t, b_t) >= _W4_MIN_WGS
 
 
-# GPT-2-sized forward products on the 128 x 128-tile kernel (csrc/kernels/gemm_s.hip): K <= 1024
-# and at least 256 output tiles. Alone (graph-timed) it runs GPT-2-small qkv 1.20x / w13 1.10x,
-# -medium qkv 1.05x / w13 1.15x hipBLASLt (profiles/r3_gemm_s_vs_hipblaslt.log), inside the
-# graph-replayed step 0.99-1.00x (profiles/r3_gpt2_s_ab.log): opt-in (set_gemm_s).
-_GEMM_S = False
+def _kernel(w4: bool, stored: bool, M: int, N: int, K: int, a_t: bool, b_t: bool, a, b) -> str:
+    """The kernel of C[M, N] over K: "w4" (its family switched on and the product routed to it), else
+    "f32" (the fp32 MFMA kernel), else "blas" (hipBLASLt). ``stored``: the operands (and the output
+    given) are contiguous -- both hand-written kernels read and write them as stored."""
+    if not stored:
+        return "blas"
+    if w4 and w4_route(M, N, K, a_t, b_t, a, b):
+        return "w4"
+    return "f32" if f32_route(M, N, K, a_t, b_t, a, b) else "blas"
 
 
-def set_gemm_s(on: bool) -> None:
-    global _GEMM_S
-    _GEMM_S = bool(on)
+def fwd_kernel(x2, w) -> str:
+    """y[T, N] = x2[T, K] w[N, K]^T (x2 is made contiguous by the caller)."""
+    return _kernel(_W4_FWD, w.is_contiguous(), x2.shape[0], w.shape[0], x2.shape[1], False, False, x2, w)
 
 
-def _s_ok(x2: torch.Tensor, w: torch.Tensor) -> bool:
-    if not (_GEMM_S and not _BLAS_ONLY and x2.is_cuda and x2.dtype in _W4_DTYPES and w.dtype == x2.dtype):
-        return False
-    T, K = x2.shape
-    N = w.shape[0]
-    return T % 128 == 0 and N % 128 == 0 and K % 64 == 0 and K <= 1024 and (T // 128) * (N // 128) >= 256
+def dx_kernel(dy2, w, out=None) -> str:
+    """dX[T, K] = dy2[T, N] w[N, K], k-major w read as stored (dy2 is made contiguous by the caller)."""
+    stored = w.is_contiguous() and (out is None or out.is_contiguous())
+    return _kernel(_W4_BWD, stored, dy2.shape[0], w.shape[1], dy2.shape[1], False, True, dy2, w)
 
 
-# A forward product on the widest (256-column) w4 tile only from K = 2048: at GPT-2 sizes (K = 768 /
-# 1024) the wide tile's prologue / epilogue outweigh its main loop (LM-head logits 439 vs 362 us
-# for hipBLASLt at K = 768, profiles/r4_gpt2_head_fwd_probe.log); the narrower tiles run there.
-_W4_WIDE_MIN_K = 2048
-
-
-def _w4_fwd_ok(T: int, N: int, K: int, x2, w) -> bool:
-    """The forward product on w4; before round 6 the 256-wide tile below K = 2048 only within one
-    round (the GPT-2-medium w1|w3: 176 tiles, 27.7 vs 35.0 us for hipBLASLt). Since round 6
-    (_W4_SMALL) the GPT-2 LM head at V = 131072, K = 768 / 1024 runs on it too: 0.79x hipBLASLt
-    there, the 128-wide tile 0.60x (profiles/r6/gpt2_gemm_probe_small.log)."""
-    if not (_W4_FWD and w.is_contiguous() and w4_route(T, N, K, False, False, x2, w)):
-        return False
-    nj, sp = _w4_plan(T, N, K, False, False)
-    return _W4_SMALL or K >= _W4_WIDE_MIN_K or nj <= 6 or (T // 256) * (N // (32 * nj)) * sp <= 256
+def dw_kernel(dy2, x2, out=None) -> str:
+    """dW[N, K] = dy2[T, N]^T x2[T, K], k-major dy2 and x2 read as stored."""
+    stored = dy2.is_contiguous() and x2.is_contiguous() and (out is None or out.is_contiguous())
+    return _kernel(_W4_BWD, stored, dy2.shape[1], x2.shape[1], dy2.shape[0], True, True, dy2, x2)
 
 
 def mm_fwd(x2: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x2 @ w^T (+ residual, in the epilogue): x2 [T, K], w [N, K] (nn.Linear layout)."""
     T, K = x2.shape
     N = w.shape[0]
+    k = fwd_kernel(x2, w)
+    if k == "blas":
+        return torch.mm(x2, w.t()) if residual is None else torch.addmm(residual.reshape(T, N), x2, w.t())
     res = None if residual is None else residual.reshape(T, N).contiguous()
-    if _s_ok(x2, w):
-        return kernels().gemm_nt_s(x2.contiguous(), w, None, res, 1)
-    if _w4_fwd_ok(T, N, K, x2, w):
+    if k == "w4":
         return kernels().gemm_nt_w4(x2.contiguous(), w, None, res, 0, 0)
-    if w.is_contiguous() and f32_route(T, N, K, False, False, x2, w):
-        return kernels().gemm_f32(x2.contiguous(), False, w, False, T, N, K, None, False, None, res)
-    if residual is None:
-        return torch.mm(x2, w.t())
-    return torch.addmm(residual.reshape(T, N), x2, w.t())
-
-
-def _w4_dx_ok(T: int, K: int, N: int, dy2: torch.Tensor, w: torch.Tensor) -> bool:
-    """dX[T, K] = dY[T, N] W[N, K] on w4 (k-major W read as stored). The deep reductions (the 8B
-    w1|w3 dX, N = 2F; the LM-head dX, N = V) whose 256-wide tiles fill half the chip take a K split
-    (profiles/r5_w4_split_bench.log)."""
-    return _W4_BWD and w.is_contiguous() and w4_route(T, K, N, False, True, dy2, w)
+    return kernels().gemm_f32(x2.contiguous(), False, w, False, T, N, K, None, False, None, res)
 
 
 def mm_dx(dy2: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dx = dy2 @ w: dy2 [T, N], w [N, K]."""
+    """dx = dy2 @ w: dy2 [T, N], w [N, K] (into ``out`` when given)."""
     T, N = dy2.shape
     K = w.shape[1]
-    if _w4_dx_ok(T, K, N, dy2, w) and (out is None or out.is_contiguous()):
+    k = dx_kernel(dy2, w, out)
+    if k == "w4":
         return kernels().gemm_w4_ex(dy2.contiguous(), False, w, True, T, K, N, out, False, None, 0, 0)
-    if w.is_contiguous() and (out is None or out.is_contiguous()) and f32_route(T, K, N, False, True, dy2, w):
+    if k == "f32":
         return kernels().gemm_f32(dy2.contiguous(), False, w, True, T, K, N, out, False, None, None)
-    if out is not None:
-        return torch.mm(dy2, w, out=out)
-    return torch.mm(dy2, w)
+    return torch.mm(dy2, w) if out is None else torch.mm(dy2, w, out=out)
 
 
-def _w4_dw_ok(T: int, N: int, K: int, dy2: torch.Tensor, x2: torch.Tensor) -> bool:
-    return (_W4_BWD and dy2.is_contiguous() and x2.is_contiguous()
-            and w4_route(N, K, T, True, True, dy2, x2))
-
-
-def _f32_dw_ok(T: int, N: int, K: int, dy2: torch.Tensor, x2: torch.Tensor) -> bool:
-    return dy2.is_contiguous() and x2.is_contiguous() and f32_route(N, K, T, True, True, dy2, x2)
-
-
-def _f32_dw(dy2, x2, out, accumulate: bool, sink: Optional[GradSink]):
-    """dW = dy2^T x2 on the fp32 MFMA kernel (k-major operands read as stored), (+)= into ``out``,
-    with the sink's norm partials (of the stored values, as the w4 dW epilogue) when ``sink`` is
-    given: the product that writes the sink's final gradient."""
+def _dw_into(out: Optional[torch.Tensor], dy2: torch.Tensor, x2: torch.Tensor, accumulate: bool,
+             sink: Optional[GradSink] = None) -> torch.Tensor:
+    """out[N, K] (+)= dy2[T, N]^T @ x2[T, K] (``out`` None: a new tensor); returns it. ``sink``:
+    this is the final write of the sink's gradient, so the w4 / fp32 MFMA epilogue leaves the norm
+    partials of the stored values."""
     T, N = dy2.shape
     K = x2.shape[1]
+    k = dw_kernel(dy2, x2, out)
+    if k == "blas":
+        if out is None:
+            return torch.mm(dy2.t(), x2)
+        return out.addmm_(dy2.t(), x2) if accumulate else torch.mm(dy2.t(), x2, out=out)
     part = sink.part if sink is not None else None
-    r = kernels().gemm_f32(dy2, True, x2, True, N, K, T, out, accumulate, part, None)
+    if k == "w4":
+        out = kernels().gemm_w4_ex(dy2, True, x2, True, N, K, T, out, accumulate, part, 0, 0)
+    else:
+        out = kernels().gemm_f32(dy2, True, x2, True, N, K, T, out, accumulate, part, None)
     if part is not None:
         sink.sq_done = True
-    return r
+    return out
 
 
 def weight_grad(dy2: torch.Tensor, x2: torch.Tensor, sink: Optional[GradSink]):
     """dW[N, K] = dy2[T, N]^T @ x2[T, K], into the sink (flat grad buffer) or returned."""
-    T, N = dy2.shape
-    K = x2.shape[1]
-    if _w4_dw_ok(T, N, K, dy2, x2):
-        # both operands read as stored (k-major A and B), straight into the sink, with the norm
-        # partials of the stored gradient from the epilogue
-        if sink is None:
-            return kernels().gemm_w4_ex(dy2, True, x2, True, N, K, T, None, False, None, 0, 0)
-        kernels().gemm_w4_ex(dy2, True, x2, True, N, K, T, sink.buf.view(N, K), sink.accumulate, sink.part, 0, 0)
-        if sink.part is not None:
-            sink.sq_done = True
-        sink.ready()
-        return None
-    if _f32_dw_ok(T, N, K, dy2, x2):
-        if sink is None:
-            return _f32_dw(dy2, x2, None, False, None)
-        _f32_dw(dy2, x2, sink.buf.view(N, K), sink.accumulate, sink)
-        sink.ready()
-        return None
-    if sink is not None:
-        sink.mm(dy2.t(), x2)
-        return None
-    return torch.mm(dy2.t(), x2)
+    if sink is None:
+        return _dw_into(None, dy2, x2, False)
+    _dw_into(sink.buf.view(dy2.shape[1], x2.shape[1]), dy2, x2, sink.accumulate, sink)
+    sink.ready()
+    return None
 
 
 # Weight-gradient GEMMs that do not take the w4 kernel (hipBLASLt: the small presets) run on a side
@@ -298,7 +244,8 @@ def weight_grad_async(dy2: torch.Tensor, x2: torch.Tensor, sink: Optional[GradSi
     dy2 = dy2.contiguous()
     x2 = x2.contiguous()
     T, N, K = dy2.shape[0], dy2.shape[1], x2.shape[1]
-    if not _W4_DW_SIDE and _w4_dw_ok(T, N, K, dy2, x2) and _w4_wgs(N, K, T, True, True) >= 256:
+    if (not _W4_DW_SIDE and _W4_BWD and w4_route(N, K, T, True, True, dy2, x2)
+            and _w4_wgs(N, K, T, True, True) >= 256):
         # a full-chip w4 dW runs inline; the GPT-2-sized ones (54-192 workgroups) run on the side
         # stream beside the dX product of the same node, which leaves the rest of the CUs idle too
         return weight_grad(dy2, x2, sink)
@@ -593,9 +540,7 @@ def _ffn_w4t_ok(x2: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor) -> bool:
     if T % 256 or D % 128:
         return False
     nj = _swiglu_nj(T, F)
-    if nj == 0 or (T // 256) * (F // (16 * nj)) < (min(_W4_MIN_TILES, _W4_SMALL_WGS) if _W4_SMALL else _W4_MIN_TILES):
-        return False
-    if not _W4_SMALL and F % 112:
+    if nj == 0 or (T // 256) * (F // (16 * nj)) < _W4_MIN_WGS:
         return False
     return (w4_route(T, F, D, False, True, x2, w2) and w4_route(2 * F, D, T, True, True, x2, w13)
             and w4_route(D, F, T, True, True, x2, w2) and w4_route(T, D, 2 * F, False, True, x2, w13))
@@ -702,27 +647,6 @@ def _head_rows(T: int, V: int) -> int:
 def _dx_into(out: torch.Tensor, dy2: torch.Tensor, w: torch.Tensor) -> None:
     """out[T, K] = dy2[T, N] @ w[N, K]."""
     mm_dx(dy2, w, out)
-
-
-def _dw_into(out: torch.Tensor, dy2: torch.Tensor, x2: torch.Tensor, accumulate: bool,
-             sink: Optional[GradSink] = None) -> None:
-    """out[N, K] (+)= dy2[T, N]^T @ x2[T, K]. ``sink``: the final write of the sink's gradient
-    (its norm partials come from this product's epilogue)."""
-    T, N = dy2.shape
-    K = x2.shape[1]
-    if _w4_dw_ok(T, N, K, dy2, x2):
-        part = sink.part if sink is not None else None
-        kernels().gemm_w4_ex(dy2, True, x2, True, N, K, T, out, accumulate, part, 0, 0)
-        if part is not None:
-            sink.sq_done = True
-        return
-    if _f32_dw_ok(T, N, K, dy2, x2) and out.is_contiguous():
-        _f32_dw(dy2, x2, out, accumulate, sink)
-        return
-    if accumulate:
-        out.addmm_(dy2.t(), x2)
-    else:
-        torch.mm(dy2.t(), x2, out=out)
 
 
 def _head_fwd(h2: torch.Tensor, w: torch.Tensor) -> torch.Tensor:

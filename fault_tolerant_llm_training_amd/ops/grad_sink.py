@@ -41,15 +41,6 @@ class GradSink:
         if self.hook is not None:
             self.hook(self)
 
-    # dW = a @ b (written or accumulated into buf)
-    def mm(self, a: torch.Tensor, b: torch.Tensor) -> None:
-        out = self.buf.view(a.shape[0], b.shape[1])
-        if self.accumulate:
-            out.addmm_(a, b)
-        else:
-            torch.mm(a, b, out=out)
-        self.ready()
-
     def set_(self, g: torch.Tensor) -> None:
         if self.accumulate:
             self.buf.add_(g.view_as(self.buf))

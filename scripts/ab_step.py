@@ -126,7 +126,6 @@ def main():
                "psums": lambda on: (torch.cuda.synchronize(), red.set_producer_sums(on)),
                "splitk": lambda on: (torch.cuda.synchronize(), Fx.set_w4_splitk(1 if on else 0)),
                "w4dwside": lambda on: (torch.cuda.synchronize(), setattr(Fx, "_W4_DW_SIDE", on)),
-               "gemm_s": lambda on: (torch.cuda.synchronize(), Fx.set_gemm_s(on)),
                "adamw_serial": lambda on: serial_adamw.__setitem__(0, bool(on)),
                "raster": lambda on: (torch.cuda.synchronize(), kernels().gemm_w4_set_group(-1 if on else 0)),
                "deadzero": lambda on: (torch.cuda.synchronize(), kernels().gemm_w4_set_deadzero(1 if on else 0)),

@@ -256,10 +256,12 @@ def test_dw_side_stream_bitwise(w4, monkeypatch):
     from fault_tolerant_llm_training_amd.parallel.ddp import GradReducer
 
     if w4:
-        monkeypatch.setattr(Fx, "_W4_MIN_TILES", 1)
-        monkeypatch.setattr(Fx, "_W4_DEEP_K", 0)
+        monkeypatch.setattr(Fx, "_W4_MIN_WGS", 1)
         monkeypatch.setattr(Fx, "_W4_DW_SIDE", True)
     a = model_args_for("tiny", vocab_size=1024, seq_len=256)
+    spec = lambda *s: torch.empty(*s, device="cuda", dtype=torch.bfloat16)  # noqa: E731
+    # the wo weight gradient of this model (512 tokens, dim 256): on w4 only with the gate lowered
+    assert (Fx.dw_kernel(spec(512, a.dim), spec(512, a.dim)) == "w4") == w4
     tok = torch.randint(0, 1024, (2, 256), device="cuda")
     lab = torch.randint(0, 1024, (2, 256), device="cuda")
     out = []
@@ -292,7 +294,7 @@ def test_weight_grad_blas_route():
 
     dy = torch.randn(256, 384, device="cuda").bfloat16()
     x = torch.randn(256, 128, device="cuda").bfloat16()
-    assert not Fx._w4_dw_ok(256, 384, 128, dy, x)
+    assert Fx.dw_kernel(dy, x) == "blas"
     dw = Fx.weight_grad(dy, x, None)
     ref = dy.float().t() @ x.float()
     assert rel(dw, ref) < 1e-2
@@ -343,8 +345,7 @@ def test_feed_forward_fused(w4, monkeypatch):
     from fault_tolerant_llm_training_amd.ops.grad_sink import GradSink
 
     if w4:
-        monkeypatch.setattr(Fx, "_W4_MIN_TILES", 1)
-        monkeypatch.setattr(Fx, "_W4_DEEP_K", 0)
+        monkeypatch.setattr(Fx, "_W4_MIN_WGS", 1)
     torch.manual_seed(5)
     T, D, Fh = 256, 256, 896  # F % 112 (SwiGLU tile), 2F % 256 (dW13 rows)
     x = torch.randn(T, D, device="cuda").bfloat16().requires_grad_(True)

@@ -1,5 +1,5 @@
-"""GEMM routing table per preset and dtype (ops/routing.py: routing_table evaluates the same
-predicates the autograd functions use, on shape/dtype specs: no GPU needed). Pins which kernel
+"""GEMM routing table per preset and dtype (ops/routing.py: routing_table asks the choosers the
+autograd functions switch on, on shape/dtype specs: no GPU needed). Pins which kernel
 each product of the step takes, so a routing change is a visible test change:
 
 * Llama-3-8B bf16 / fp16: every product on the hand-written w4 kernel -- none on hipBLASLt (the
@@ -45,14 +45,49 @@ def test_fp32_takes_the_f32_mfma_gemm_and_cpu_the_composed_path(preset, monkeypa
     assert set(routing_table(a, torch.float32).values()) == {"hipBLASLt"}
 
 
+# bf16 and fp16 alike; the layer rows do not depend on the vocabulary
+GPT2_TABLES = {
+    ("gpt2-small", 50304): {
+        "qkv fwd": "w4 128", "qkv dX": "w4 128 x2", "qkv dW": "w4 128 x2",
+        "wo fwd": "w4 128", "wo dX": "w4 128", "wo dW": "w4 128 x2",
+        "w13 fwd": "w4 swiglu", "w2 dX": "w4 swiglu-bwd", "w13 dX": "w4 128 x3", "w13 dW": "w4 128 x2",
+        "w2 fwd": "w4 128 x2", "w2 dW": "w4 128 x2",
+        "head fwd": "w4 192", "head dX": "w4 192 x8", "head dW": "w4 256",
+    },
+    ("gpt2-small", 131072): {
+        "qkv fwd": "w4 128", "qkv dX": "w4 128 x2", "qkv dW": "w4 128 x2",
+        "wo fwd": "w4 128", "wo dX": "w4 128", "wo dW": "w4 128 x2",
+        "w13 fwd": "w4 swiglu", "w2 dX": "w4 swiglu-bwd", "w13 dX": "w4 128 x3", "w13 dW": "w4 128 x2",
+        "w2 fwd": "w4 128 x2", "w2 dW": "w4 128 x2",
+        "head fwd": "w4 256", "head dX": "w4 192 x8", "head dW": "w4 256",
+    },
+    ("gpt2-medium", 50304): {
+        "qkv fwd": "w4 128", "qkv dX": "w4 128 x3", "qkv dW": "w4 128 x2",
+        "wo fwd": "w4 128", "wo dX": "w4 128", "wo dW": "w4 128 x2",
+        "w13 fwd": "w4 swiglu", "w2 dX": "w4 swiglu-bwd", "w13 dX": "w4 128 x4", "w13 dW": "w4 128",
+        "w2 fwd": "w4 128 x3", "w2 dW": "w4 128 x2",
+        "head fwd": "w4 192", "head dX": "w4 128 x4", "head dW": "w4 256",
+    },
+    ("gpt2-medium", 131072): {
+        "qkv fwd": "w4 128", "qkv dX": "w4 128 x3", "qkv dW": "w4 128 x2",
+        "wo fwd": "w4 128", "wo dX": "w4 128", "wo dW": "w4 128 x2",
+        "w13 fwd": "w4 swiglu", "w2 dX": "w4 swiglu-bwd", "w13 dX": "w4 128 x4", "w13 dW": "w4 128",
+        "w2 fwd": "w4 128 x3", "w2 dW": "w4 128 x2",
+        "head fwd": "w4 256", "head dX": "w4 256 x8", "head dW": "w4 256",
+    },
+}
+
+
 @pytest.mark.parametrize("preset,vocab", [("gpt2-small", 50304), ("gpt2-small", 131072),
                                           ("gpt2-medium", 50304), ("gpt2-medium", 131072)])
 def test_gpt2_routes(preset, vocab):
-    """Round 6: no GPT-2 product on hipBLASLt. The 18-96-tile weight gradients take a K split (the
+    """No GPT-2 product on hipBLASLt. The 18-96-tile weight gradients take a K split (the
     dW layout splits its 128-wide tile), the 2048-3072-deep forward / dX products too, the FFN runs
     fused (SwiGLU in the w1|w3 epilogue, its backward in the w2 dX epilogue), the LM-head dW at the
     padded V = 50304 a tail tile, the V = 131072 logits the 256-wide tile (K = 768 / 1024)."""
-    t = routing_table(model_args_for(preset, vocab_size=vocab, seq_len=2048), torch.bfloat16)
+    a = model_args_for(preset, vocab_size=vocab, seq_len=2048)
+    t = routing_table(a, torch.bfloat16)
+    assert t == GPT2_TABLES[preset, vocab] == routing_table(a, torch.float16)
     assert sorted(t) == sorted(PRODUCTS)
     assert "hipBLASLt" not in t.values(), t
     assert t["head dX"].startswith("w4") and " x" in t["head dX"]
@@ -65,11 +100,18 @@ def test_gpt2_routes(preset, vocab):
         assert t["head fwd"] == "w4 256"
 
 
-def test_gpt2_round5_routing_knob(monkeypatch):
-    """set_w4_small(False) (FT_W4_SMALL=0): the round-5 routing of the small products (A/B)."""
-    monkeypatch.setattr(Fx, "_W4_SMALL", False)
-    t = routing_table(model_args_for("gpt2-small", vocab_size=50304, seq_len=2048), torch.bfloat16)
-    assert t["wo dW"] == t["head dW"] == "hipBLASLt" and t["wo fwd"] == "w4 128"
+def test_table_reads_the_choosers(monkeypatch):
+    """The table is the answer of the chooser mm_fwd switches on, not a copy of its order: with
+    ``fwd_kernel`` replaced, every forward row changes and no other row does. (The fused FFN node
+    is switched off so that the w1|w3 forward is a plain product too; GPT-2's QKV is one already.)"""
+    monkeypatch.setattr(Fx, "_W4_SWIGLU", False)
+    a = model_args_for("gpt2-small", vocab_size=50304, seq_len=2048)
+    before = routing_table(a, torch.bfloat16)
+    fwd_rows = [k for k in PRODUCTS if k.endswith(" fwd")]
+    assert len(fwd_rows) == 5 and all(before[k].startswith("w4 ") for k in fwd_rows), before
+    monkeypatch.setattr(Fx, "fwd_kernel", lambda x2, w: "blas")
+    after = routing_table(a, torch.bfloat16)
+    assert after == {k: "hipBLASLt" if k in fwd_rows else v for k, v in before.items()}
 
 
 def test_blas_only_knob(monkeypatch):

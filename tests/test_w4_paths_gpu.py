@@ -1,8 +1,8 @@
 """The model's w4-kernel backward paths end to end, on a small model driven through them.
 
-The w4 routing only takes products with at least half the chip in output tiles (and the fused
-QKV + RoPE projection only from model dim 2048), so the tiny / GPT-2 GPU tests never reach it.
-Here those gates are lowered (``_W4_MIN_TILES``, ``_W4_DEEP_K``, ``_QKV_ROPE_MIN_K``) and a Llama-style model
+The w4 routing only takes products whose plan has at least 16 workgroups (and the fused QKV + RoPE
+projection only from model dim 2048 and half the chip in output tiles), so the tiny GPU tests never reach it.
+Here those gates are lowered (``_W4_MIN_WGS``, ``_QKV_ROPE_MIN_TILES``, ``_QKV_ROPE_MIN_K``) and a Llama-style model
 whose FFN width is a multiple of 112 (the SwiGLU-epilogue tile) runs:
   forward  QKV GEMM with the RoPE epilogue, wo / w2 with the residual epilogue, w1|w3 with the
            SwiGLU epilogue, the LM head on the w4 kernel
@@ -27,11 +27,10 @@ def rel(a, b):
 def gates(monkeypatch):
     from fault_tolerant_llm_training_amd.ops import functional as Fx
 
-    monkeypatch.setattr(Fx, "_W4_MIN_TILES", 1)
-
-    monkeypatch.setattr(Fx, "_W4_DEEP_K", 0)
+    monkeypatch.setattr(Fx, "_W4_MIN_WGS", 1)
     from fault_tolerant_llm_training_amd.ops import attention as A
 
+    monkeypatch.setattr(A, "_QKV_ROPE_MIN_TILES", 1)
     monkeypatch.setattr(A, "_QKV_ROPE_MIN_K", 0)
     return Fx
 
@@ -188,6 +187,8 @@ def test_fused_sumsq_fallback_then_producer(gates):
     m = build_model(a, "cuda", torch.bfloat16, seed=3)
     red = ddp.GradReducer(m.flat, m.sinks_in_backward_order(), bucket_mb=1.0)
     assert red.fused_sumsq
+    x2 = torch.empty(a.seq_len, a.dim, device="cuda", dtype=torch.bfloat16)
+    assert gates.dw_kernel(x2, x2) == "w4"  # (the wo weight gradient) the producers are the w4 epilogues
     torch.manual_seed(2)
     for it, producers in enumerate([False, True, True]):
         torch.cuda.synchronize()
