@@ -1,0 +1,696 @@
+// Text generation: the one-row (decode) kernels. The reference has no generation path at all; the
+// math is its model (model.py:179-215, :253-254, :379) applied to one new token against a cache of
+// the earlier tokens' rotated K and V.
+//
+// Decoding is a different regime from every other file here: one activation row against all the
+// weights, so every kernel is bound by HBM bandwidth and is plain vector code -- 16-byte loads
+// straight into registers, several in flight per lane, fp32 accumulation, no LDS staging of the
+// streamed operand, no matrix cores, no inline assembly.
+//
+//   gemv                y[N] = W[N, K] x[K] (+ residual[N])        one wave per output row
+//   gemv_swiglu         a[H] = silu(w1 x) * (w3 x) from [w1; w3]    one wave per feature, both rows
+//   decode_qkv_append_  RoPE at `pos` on Q (in place) and K (into k_cache[:, pos]); V into v_cache[:, pos]
+//   decode_attn         one query over keys 0 .. n_keys-1 of the cache, GQA indexed in place
+//   sample_             one token per row of logits: greedy, or temperature / top-k sampling
+//
+// Reproducibility: nothing on a result path is accumulated with atomics and every reduction has a
+// fixed order (per-lane sweep, xor butterfly over the wave, waves in index order, key chunks in
+// chunk order), so each op returns the same bits from run to run. The sampler's top-k threshold is
+// found with integer histograms in LDS (integer counts do not depend on the order of the adds).
+//
+// Positions, key counts and the sampler's step are host integers (kernel arguments).
+#include <climits>
+
+#include "sround.h"
+#include "torch_utils.h"
+
+namespace {
+
+constexpr float LOG2E = 1.4426950408889634f;
+// keys per workgroup of decode_attn; the chunk partials are merged in chunk order
+constexpr int DECODE_CHUNK = 128;
+constexpr int SAMPLE_MAX_BLOCKS = 32768;
+
+// ---- one 16-byte vector of the model dtype: 8 elements (bf16 / fp16) or 4 (fp32)
+template <class E>
+struct V16 {
+  static constexpr int N = E::is16 ? 8 : 4;
+};
+
+template <class E>
+__device__ __forceinline__ void unpv(const uint4& v, float* f) {
+  if constexpr (E::is16) {
+    unpack8e<E>(v, f);
+  } else {
+    f[0] = __uint_as_float(v.x);
+    f[1] = __uint_as_float(v.y);
+    f[2] = __uint_as_float(v.z);
+    f[3] = __uint_as_float(v.w);
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// gemv / gemv_swiglu. One wave per output row (SWIGLU: rows h and H + h of [w1; w3]); lane l takes
+// the 16-byte vectors l, l + 64, ... of the row, four of them in flight per row, each into its own
+// fp32 accumulator; x comes from the cache (every wave reads the same K elements). The lane sums
+// are added as (a0 + a1) + (a2 + a3), then the xor butterfly over the wave.
+// --------------------------------------------------------------------------------------------
+template <class E, int VN>
+__device__ __forceinline__ float dotv(const uint4& wv, const float* xf, float acc) {
+  float wf[8];
+  unpv<E>(wv, wf);
+#pragma unroll
+  for (int j = 0; j < VN; ++j) acc = fmaf(wf[j], xf[j], acc);
+  return acc;
+}
+
+template <class E, bool SWIGLU>
+__global__ __launch_bounds__(256) void gemv_kernel(const typename E::T* __restrict__ x,
+                                                   const typename E::T* __restrict__ w,
+                                                   const typename E::T* __restrict__ res,
+                                                   typename E::T* __restrict__ y, int N, int K) {
+  constexpr int VN = V16<E>::N;
+  constexpr int STEP = 64 * VN;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;  // whole waves leave; the kernel has no block barrier
+  const typename E::T* w0 = w + (long)row * K;
+  const typename E::T* w1 = w + ((long)row + N) * K;  // SWIGLU only: the w3 row of feature `row`
+  float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
+  int k = lane * VN;
+  for (; k + 3 * STEP < K; k += 4 * STEP) {
+    uint4 wv[4], uv[4], xv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      wv[u] = *reinterpret_cast<const uint4*>(w0 + k + u * STEP);
+      if constexpr (SWIGLU) uv[u] = *reinterpret_cast<const uint4*>(w1 + k + u * STEP);
+      xv[u] = *reinterpret_cast<const uint4*>(x + k + u * STEP);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float xf[8];
+      unpv<E>(xv[u], xf);
+      a[u] = dotv<E, VN>(wv[u], xf, a[u]);
+      if constexpr (SWIGLU) b[u] = dotv<E, VN>(uv[u], xf, b[u]);
+    }
+  }
+  for (; k < K; k += STEP) {
+    float xf[8];
+    unpv<E>(*reinterpret_cast<const uint4*>(x + k), xf);
+    a[0] = dotv<E, VN>(*reinterpret_cast<const uint4*>(w0 + k), xf, a[0]);
+    if constexpr (SWIGLU) b[0] = dotv<E, VN>(*reinterpret_cast<const uint4*>(w1 + k), xf, b[0]);
+  }
+  float s = wave_sum((a[0] + a[1]) + (a[2] + a[3]));
+  if constexpr (SWIGLU) {
+    const float t = wave_sum((b[0] + b[1]) + (b[2] + b[3]));
+    if (lane == 0) {
+      // g, u and silu(g) each rounded to the model dtype: the composed gemv -> silu -> mul
+      const float g = rnd<E>(s), u = rnd<E>(t);
+      const float sl = rnd<E>(g / (1.f + expf(-g)));
+      y[row] = cvt1<E>(sl * u);
+    }
+  } else if (lane == 0) {
+    if (res != nullptr) s += ld1<E>(res + row);
+    y[row] = cvt1<E>(s);
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// decode_qkv_append_: qkv [(Hq + 2 Hkv) D] of the new token. One thread per 8 columns (4 pairs).
+// --------------------------------------------------------------------------------------------
+template <class E>
+__global__ __launch_bounds__(256) void qkv_append_kernel(typename E::T* __restrict__ qkv,
+                                                         const float* __restrict__ cos_row,
+                                                         const float* __restrict__ sin_row,
+                                                         typename E::T* __restrict__ kc,
+                                                         typename E::T* __restrict__ vc, int hq, int hkv, int d,
+                                                         long smax, long pos) {
+  const int nvec = (hq + 2 * hkv) * d / 8;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nvec) return;
+  const int col = i * 8, head = col / d, within = col - head * d;
+  float x[8];
+  ld8<E>(qkv + col, x);
+  if (head < hq + hkv) {
+    const float4 c = *reinterpret_cast<const float4*>(cos_row + (within >> 1));
+    const float4 s = *reinterpret_cast<const float4*>(sin_row + (within >> 1));
+    const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {s.x, s.y, s.z, s.w};
+    float r[8];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const float a = x[2 * p], b = x[2 * p + 1];
+      r[2 * p] = a * cc[p] - b * ss[p];
+      r[2 * p + 1] = a * ss[p] + b * cc[p];
+    }
+    if (head < hq) st8<E>(qkv + col, r);
+    else st8<E>(kc + ((long)(head - hq) * smax + pos) * d + within, r);
+  } else {
+    st8<E>(vc + ((long)(head - hq - hkv) * smax + pos) * d + within, x);
+  }
+}
+
+// --------------------------------------------------------------------------------------------
+// decode_attn. Workgroup (kv head, chunk of DECODE_CHUNK keys), 256 threads. D / 8 lanes share a key
+// row (16 bytes of it each), so a pass covers 256 / (D / 8) keys; every K and V row is loaded once
+// and used for all the G = Hq / Hkv query heads of the group (in tiles of GT heads: one tile for
+// G <= 8). Per head the workgroup leaves (acc[D] unnormalised, m, l) of its chunk; the merge
+// kernel folds the chunks in chunk order. Keys at and beyond n_keys are never loaded.
+// --------------------------------------------------------------------------------------------
+template <class E, int D, int GT>
+__global__ __launch_bounds__(256) void decode_attn_kernel(const typename E::T* __restrict__ q,
+                                                          const typename E::T* __restrict__ kc,
+                                                          const typename E::T* __restrict__ vc,
+                                                          float* __restrict__ part, int hq, int hkv, long smax,
+                                                          int n_keys, float scale) {
+  constexpr int LPK = D / 8;     // lanes per key row
+  constexpr int KPP = 256 / LPK;  // keys per pass
+  __shared__ float sq[GT * D];
+  __shared__ float sp[GT][DECODE_CHUNK];
+  __shared__ float sred[4][GT][D];
+  __shared__ float s_m[GT], s_l[GT];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int sub = tid % LPK, kslot = tid / LPK;
+  const int kvh = blockIdx.x, chunk = blockIdx.y;
+  const int G = hq / hkv;
+  const int k0 = chunk * DECODE_CHUNK;
+  const int nk = min(DECODE_CHUNK, n_keys - k0);  // >= 1: the grid covers ceil(n_keys / chunk) chunks
+  const typename E::T* kbase = kc + ((long)kvh * smax + k0) * D;
+  const typename E::T* vbase = vc + ((long)kvh * smax + k0) * D;
+  for (int g0 = 0; g0 < G; g0 += GT) {
+    for (int i = tid; i < GT * D; i += 256)
+      sq[i] = (g0 + i / D < G) ? ld1<E>(q + ((long)kvh * G + g0) * D + i) : 0.f;
+    __syncthreads();
+    // scores of the chunk: sp[g][key] = scale * <q_g, k_key>, -inf beyond the live keys
+    for (int kk = kslot; kk < DECODE_CHUNK; kk += KPP) {
+      const bool live = kk < nk;
+      float kx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (live) ld8<E>(kbase + (long)kk * D + sub * 8, kx);
+#pragma unroll
+      for (int g = 0; g < GT; ++g) {
+        float dp = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) dp = fmaf(kx[j], sq[g * D + sub * 8 + j], dp);
+#pragma unroll
+        for (int o = LPK / 2; o > 0; o >>= 1) dp += __shfl_xor(dp, o, 64);
+        if (sub == 0) sp[g][kk] = live ? dp * scale : -INFINITY;
+      }
+    }
+    __syncthreads();
+    // per head: chunk maximum, p = exp(s - m), l = sum p (one wave per head)
+    for (int g = wid; g < GT; g += 4) {
+      float m = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < DECODE_CHUNK / 64; ++i) m = fmaxf(m, sp[g][lane + 64 * i]);
+      m = wave_max(m);
+      float l = 0.f;
+#pragma unroll
+      for (int i = 0; i < DECODE_CHUNK / 64; ++i) {
+        const float p = exp2f((sp[g][lane + 64 * i] - m) * LOG2E);
+        sp[g][lane + 64 * i] = p;
+        l += p;
+      }
+      l = wave_sum(l);
+      if (lane == 0) {
+        s_m[g] = m;
+        s_l[g] = l;
+      }
+    }
+    __syncthreads();
+    // acc[g][8 dims of this thread] over the thread's keys, then over the key slots
+    float acc[GT][8];
+#pragma unroll
+    for (int g = 0; g < GT; ++g)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[g][j] = 0.f;
+    for (int kk = kslot; kk < nk; kk += KPP) {
+      float vx[8];
+      ld8<E>(vbase + (long)kk * D + sub * 8, vx);
+#pragma unroll
+      for (int g = 0; g < GT; ++g) {
+        const float p = sp[g][kk];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[g][j] = fmaf(p, vx[j], acc[g][j]);
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < GT; ++g)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        float v = acc[g][j];
+#pragma unroll
+        for (int o = LPK; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+        if (lane < LPK) sred[wid][g][sub * 8 + j] = v;
+      }
+    __syncthreads();
+    for (int i = tid; i < GT * D; i += 256) {
+      const int g = i / D, dd = i - g * D;
+      if (g0 + g < G) {
+        const float v = ((sred[0][g][dd] + sred[1][g][dd]) + sred[2][g][dd]) + sred[3][g][dd];
+        part[((long)chunk * hq + (long)kvh * G + g0 + g) * (D + 2) + dd] = v;
+      }
+    }
+    if (tid < GT && g0 + tid < G) {
+      float* pr = part + ((long)chunk * hq + (long)kvh * G + g0 + tid) * (D + 2) + D;
+      pr[0] = s_m[tid];
+      pr[1] = s_l[tid];
+    }
+    __syncthreads();  // the next tile reuses the shared arrays
+  }
+}
+
+// One workgroup per query head, one thread per dim: the chunk partials in chunk order.
+template <class E, int D>
+__global__ __launch_bounds__(D) void decode_attn_merge_kernel(const float* __restrict__ part,
+                                                              typename E::T* __restrict__ o, int hq,
+                                                              int nchunks) {
+  const int h = blockIdx.x, dd = threadIdx.x;
+  float M = -INFINITY, L = 0.f, A = 0.f;
+  for (int c = 0; c < nchunks; ++c) {
+    const float* pr = part + ((long)c * hq + h) * (D + 2);
+    const float m = pr[D], l = pr[D + 1], a = pr[dd];
+    const float nM = fmaxf(M, m);
+    const float f0 = exp2f((M - nM) * LOG2E), f1 = exp2f((m - nM) * LOG2E);
+    A = A * f0 + a * f1;
+    L = L * f0 + l * f1;
+    M = nM;
+  }
+  o[(long)h * D + dd] = cvt1<E>(A / L);
+}
+
+// --------------------------------------------------------------------------------------------
+// sample_. One 256-thread workgroup per row, rows grid-strided. The row is swept in vectors of 8
+// columns, thread t taking vectors t, t + 256, ... (coalesced); "in ascending column order" is kept
+// by a block scan per sweep of 2048 columns and a running prefix over the sweeps.
+//
+//   pass A      row maximum and its lowest column (greedy ends here)
+//   passes B    top-k only: the k-th largest value by a 4 x 8-bit radix select over an
+//               order-preserving integer image of the logits (NaN lowest, -0 = +0), and how many of
+//               the columns equal to it are taken; then, if not all of them, the column of the last
+//               one taken (ties go to the lower index)
+//   pass C      total = sum of the candidates' weights exp((x - max) / temperature): fp32 weights,
+//               summed in fp64 (its rounding is far below the weights' own)
+//   pass D      the first candidate, in column order, whose cumulative weight reaches u * total
+// --------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t okey(float f) {
+  if (f != f) return 0u;
+  f += 0.f;  // -0 -> +0
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Exclusive prefix of v over the 256 threads in thread order (`total`: the sum of all of them).
+template <class T>
+__device__ __forceinline__ T block_scan(T v, T* sh, T& total) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  T inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  T ex = __shfl_up(inc, 1, 64);
+  if (lane == 0) ex = T(0);
+  if (lane == 63) sh[wid] = inc;
+  __syncthreads();
+  T off = T(0);
+  for (int i = 0; i < wid; ++i) off += sh[i];
+  total = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  __syncthreads();
+  return off + ex;
+}
+
+__device__ __forceinline__ int block_min(int v, int* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = min(min(sh[0], sh[1]), min(sh[2], sh[3]));
+  __syncthreads();
+  return v;
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void sample_kernel(const typename E::T* __restrict__ logits,
+                                                     int64_t* __restrict__ out, int V, int R, float temperature,
+                                                     int top_k, uint32_t key_lo, uint32_t key_hi, uint32_t step) {
+  __shared__ float sh_m[4];
+  __shared__ int sh_i[4];
+  __shared__ double sh_d[4];
+  __shared__ int hist[256];
+  __shared__ uint32_t s_prefix;
+  __shared__ int s_kk, s_cnt, s_tie;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const bool all = top_k <= 0 || top_k >= V;
+  for (int row = blockIdx.x; row < R; row += gridDim.x) {
+    const typename E::T* lr = logits + (long)row * V;
+    // ---- pass A: the maximum and the lowest column that attains it
+    float m = -INFINITY;
+    int mi = INT_MAX;
+    for (int c = tid * 8; c < V; c += 2048) {
+      float x[8];
+      ld8<E>(lr + c, x);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (x[j] > m || (x[j] == m && c + j < mi)) {
+          m = x[j];
+          mi = c + j;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float om = __shfl_xor(m, o, 64);
+      const int oi = __shfl_xor(mi, o, 64);
+      if (om > m || (om == m && oi < mi)) {
+        m = om;
+        mi = oi;
+      }
+    }
+    if (lane == 0) {
+      sh_m[wid] = m;
+      sh_i[wid] = mi;
+    }
+    __syncthreads();
+    m = sh_m[0];
+    mi = sh_i[0];
+    for (int i = 1; i < 4; ++i)
+      if (sh_m[i] > m || (sh_m[i] == m && sh_i[i] < mi)) {
+        m = sh_m[i];
+        mi = sh_i[i];
+      }
+    __syncthreads();
+    if (mi == INT_MAX) mi = 0;  // a row without a single ordered value (all NaN)
+    if (temperature == 0.f) {
+      if (tid == 0) out[row] = mi;
+      continue;
+    }
+    // ---- passes B: candidates are key > thr, or key == thr at a column <= tie_last
+    uint32_t thr = 0u;
+    int tie_last = V;
+    if (!all) {
+      uint32_t prefix = 0u;
+      int kk = top_k, cnt_eq = 0;
+      for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t hi_mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+        hist[tid] = 0;
+        __syncthreads();
+        for (int c = tid * 8; c < V; c += 2048) {
+          float x[8];
+          ld8<E>(lr + c, x);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const uint32_t key = okey(x[j]);
+            if ((key & hi_mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
+          }
+        }
+        __syncthreads();
+        if (tid == 0) {
+          int cum = 0, b = 255;
+          for (; b > 0; --b) {
+            if (cum + hist[b] >= kk) break;
+            cum += hist[b];
+          }
+          s_prefix = prefix | ((uint32_t)b << shift);
+          s_kk = kk - cum;
+          s_cnt = hist[b];
+        }
+        __syncthreads();
+        prefix = s_prefix;
+        kk = s_kk;
+        cnt_eq = s_cnt;
+      }
+      thr = prefix;
+      if (kk < cnt_eq) {  // only the kk lowest columns of those equal to the threshold
+        int run = 0;
+        for (int c0 = 0; c0 < V; c0 += 2048) {
+          const int c = c0 + tid * 8;
+          uint32_t eq = 0u;
+          if (c < V) {
+            float x[8];
+            ld8<E>(lr + c, x);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) eq |= (okey(x[j]) == thr ? 1u : 0u) << j;
+          }
+          const int cnt = __popc(eq);
+          int tot;
+          const int before = run + block_scan<int>(cnt, sh_i, tot);
+          if (before < kk && kk <= before + cnt) {
+            int r = before;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              if ((eq >> j) & 1u) {
+                if (++r == kk) s_tie = c + j;
+              }
+          }
+          run += tot;
+          __syncthreads();
+          if (run >= kk) break;  // uniform: run is the same in every thread
+        }
+        tie_last = s_tie;
+      }
+    }
+    auto weight = [&](float x, int col) -> float {
+      if (!(x == x)) return 0.f;
+      if (!all) {
+        const uint32_t key = okey(x);
+        if (!(key > thr || (key == thr && col <= tie_last))) return 0.f;
+      }
+      return expf((x - m) / temperature);
+    };
+    // ---- pass C: the total weight
+    double total = 0.0;
+    for (int c0 = 0; c0 < V; c0 += 2048) {
+      const int c = c0 + tid * 8;
+      double loc = 0.0;
+      if (c < V) {
+        float x[8];
+        ld8<E>(lr + c, x);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) loc += (double)weight(x[j], c + j);
+      }
+      double tot;
+      block_scan<double>(loc, sh_d, tot);
+      total += tot;
+    }
+    const uint32_t w0 = sr_bits8(key_lo, key_hi, step, SR_BUF_SAMPLE, (uint64_t)row).x;
+    const double target = ((double)w0 + 0.5) * (1.0 / 4294967296.0) * total;
+    // ---- pass D: the first candidate whose cumulative weight reaches the target
+    double run = 0.0;
+    int found = INT_MAX, last = -1;
+    for (int c0 = 0; c0 < V; c0 += 2048) {
+      const int c = c0 + tid * 8;
+      float wv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      double loc = 0.0;
+      if (c < V) {
+        float x[8];
+        ld8<E>(lr + c, x);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          wv[j] = weight(x[j], c + j);
+          loc += (double)wv[j];
+          if (wv[j] > 0.f) last = c + j;
+        }
+      }
+      double tot;
+      const double ex = block_scan<double>(loc, sh_d, tot);
+      if (run + tot >= target) {  // uniform
+        int mine = INT_MAX;
+        double cum = run + ex;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          cum += (double)wv[j];
+          if (wv[j] > 0.f && cum >= target && mine == INT_MAX) mine = c + j;
+        }
+        found = block_min(mine, sh_i);
+        if (found != INT_MAX) break;
+      }
+      run += tot;
+    }
+    if (found == INT_MAX) {  // rounding left the last cumulative sum a hair below the target
+      last = -block_min(-last, sh_i);
+      found = last >= 0 ? last : mi;
+    }
+    if (tid == 0) out[row] = found;
+    __syncthreads();
+  }
+}
+
+void check_vec(const char* op, const at::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
+}
+
+template <bool SWIGLU>
+at::Tensor gemv_impl(const char* op, const at::Tensor& x, const at::Tensor& w,
+                     const c10::optional<at::Tensor>& residual) {
+  FT_CHECK_MODEL_DTYPE(w);
+  check_vec(op, x, "x");
+  check_vec(op, w, "w");
+  TORCH_CHECK(x.scalar_type() == w.scalar_type() && x.device() == w.device(), op, ": x / w dtype or device mismatch");
+  TORCH_CHECK(w.dim() == 2 && x.dim() == 1 && x.size(0) == w.size(1), op, ": x [K], w [N, K]");
+  const int64_t rows = w.size(0), K = w.size(1);
+  const int vn = w.scalar_type() == at::kFloat ? 4 : 8;
+  TORCH_CHECK(K > 0 && K % vn == 0, op, ": K must be a positive multiple of ", vn, " (16-byte row vectors)");
+  TORCH_CHECK(rows > 0 && rows <= INT_MAX && K <= INT_MAX, op, ": N and K must fit 32 bits");
+  TORCH_CHECK(!SWIGLU || rows % 2 == 0, op, ": w13 must be [2H, K]");
+  const int64_t N = SWIGLU ? rows / 2 : rows;
+  const bool has_res = residual.has_value() && residual->defined();
+  if (has_res) {
+    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() && residual->scalar_type() == w.scalar_type() &&
+                    residual->device() == w.device() && residual->numel() == N,
+                op, ": residual must be a contiguous [N] tensor of w's dtype and device");
+  }
+  const at::DeviceGuard guard(w.device());
+  auto y = at::empty({N}, w.options());
+  FT_DISPATCH_E(w.scalar_type(),
+                hipLaunchKernelGGL((gemv_kernel<E, SWIGLU>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ft_stream(),
+                                   cptr<typename E::T>(x), cptr<typename E::T>(w),
+                                   has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y),
+                                   (int)N, (int)K));
+  FT_LAUNCH_CHECK();
+  return y;
+}
+
+void check_cache(const char* op, const at::Tensor& c, const at::Tensor& like, int64_t hkv, int64_t d) {
+  TORCH_CHECK(c.is_cuda() && c.device() == like.device() && c.scalar_type() == like.scalar_type(), op,
+              ": the caches must be on qkv's device, in its dtype");
+  TORCH_CHECK(c.is_contiguous() && c.dim() == 3 && c.size(0) == hkv && c.size(2) == d, op,
+              ": a cache is a contiguous [Hkv, Smax, D] tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, op, ": a cache must be 16-byte aligned");
+}
+
+template <class E, int D>
+void launch_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& part,
+                 const at::Tensor& o, int hq, int hkv, int n_keys, int nchunks) {
+  const int G = hq / hkv;
+  const dim3 grid(hkv, nchunks);
+  const float scale = 1.f / sqrtf((float)D);
+  const long smax = kc.size(1);
+#define FT_ATTN(GT)                                                                                        \
+  hipLaunchKernelGGL((decode_attn_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(), cptr<typename E::T>(q), \
+                     cptr<typename E::T>(kc), cptr<typename E::T>(vc), mptr<float>(part), hq, hkv, smax, n_keys, scale)
+  if (G == 1) FT_ATTN(1);
+  else if (G == 2) FT_ATTN(2);
+  else if (G <= 4) FT_ATTN(4);
+  else FT_ATTN(8);
+#undef FT_ATTN
+  FT_LAUNCH_CHECK();
+  hipLaunchKernelGGL((decode_attn_merge_kernel<E, D>), dim3(hq), dim3(D), 0, ft_stream(), cptr<float>(part),
+                     mptr<typename E::T>(o), hq, nchunks);
+}
+
+}  // namespace
+
+// y[N] = w[N, K] x[K] (+ residual[N]), fp32 accumulation, one rounding per output.
+at::Tensor gemv(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
+  return gemv_impl<false>("gemv", x, w, residual);
+}
+
+// a[H] = silu(w1 x) * (w3 x) from the fused [w1; w3] view [2H, K].
+at::Tensor gemv_swiglu(const at::Tensor& x, const at::Tensor& w13) {
+  return gemv_impl<true>("gemv_swiglu", x, w13, c10::nullopt);
+}
+
+// qkv [(hq + 2 hkv) d] of the token at `pos`: Q rotated in place, K rotated into k_cache[:, pos],
+// V copied into v_cache[:, pos]. Caches: [hkv, Smax, d].
+void decode_qkv_append_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t, int64_t pos,
+                        const at::Tensor& k_cache, const at::Tensor& v_cache) {
+  FT_CHECK_MODEL_DTYPE(qkv);
+  check_vec("decode_qkv_append_", qkv, "qkv");
+  TORCH_CHECK(k_cache.dim() == 3, "decode_qkv_append_: a cache is [Hkv, Smax, D]");
+  const int64_t hkv = k_cache.size(0), smax = k_cache.size(1), d = k_cache.size(2);
+  check_cache("decode_qkv_append_", k_cache, qkv, hkv, d);
+  check_cache("decode_qkv_append_", v_cache, qkv, hkv, d);
+  TORCH_CHECK(v_cache.size(1) == smax, "decode_qkv_append_: k_cache / v_cache length mismatch");
+  TORCH_CHECK(d > 0 && d % 8 == 0, "decode_qkv_append_: head_dim must be a multiple of 8");
+  TORCH_CHECK(qkv.numel() % d == 0 && qkv.numel() / d > 2 * hkv, "decode_qkv_append_: qkv width");
+  const int64_t hq = qkv.numel() / d - 2 * hkv;
+  TORCH_CHECK(pos >= 0 && pos < smax, "decode_qkv_append_: pos ", pos, " outside the cache [0, ", smax, ")");
+  for (const at::Tensor* t : {&cos_t, &sin_t}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
+                    t->dim() == 2 && t->size(1) == d / 2 && t->size(0) > pos,
+                "decode_qkv_append_: cos / sin must be fp32 [S > pos, D / 2] on qkv's device");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "decode_qkv_append_: cos / sin alignment");
+  }
+  const at::DeviceGuard guard(qkv.device());
+  const int nvec = (int)(qkv.numel() / 8);
+  FT_DISPATCH_E(qkv.scalar_type(),
+                hipLaunchKernelGGL(qkv_append_kernel<E>, dim3((nvec + 255) / 256), dim3(256), 0, ft_stream(),
+                                   mptr<typename E::T>(qkv), cptr<float>(cos_t) + pos * (d / 2),
+                                   cptr<float>(sin_t) + pos * (d / 2), mptr<typename E::T>(k_cache),
+                                   mptr<typename E::T>(v_cache), (int)hq, (int)hkv, (int)d, (long)smax, (long)pos));
+  FT_LAUNCH_CHECK();
+}
+
+// o[hq d] = softmax(q K^T / sqrt(d)) V over keys 0 .. n_keys-1 of the caches [hkv, Smax, d].
+at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t n_keys) {
+  FT_CHECK_MODEL_DTYPE(q);
+  check_vec("decode_attn", q, "q");
+  TORCH_CHECK(k_cache.dim() == 3, "decode_attn: a cache is [Hkv, Smax, D]");
+  const int64_t hkv = k_cache.size(0), smax = k_cache.size(1), d = k_cache.size(2);
+  check_cache("decode_attn", k_cache, q, hkv, d);
+  check_cache("decode_attn", v_cache, q, hkv, d);
+  TORCH_CHECK(v_cache.size(1) == smax, "decode_attn: k_cache / v_cache length mismatch");
+  TORCH_CHECK(d == 64 || d == 128, "decode_attn: head_dim must be 64 or 128");
+  TORCH_CHECK(q.numel() % d == 0, "decode_attn: q width");
+  const int64_t hq = q.numel() / d;
+  TORCH_CHECK(hq > 0 && hq % hkv == 0, "decode_attn: Hq must be a multiple of Hkv");
+  TORCH_CHECK(n_keys >= 1 && n_keys <= smax && smax <= INT_MAX, "decode_attn: n_keys ", n_keys,
+              " outside [1, Smax = ", smax, "]");
+  const at::DeviceGuard guard(q.device());
+  const int nchunks = (int)((n_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
+  TORCH_CHECK(nchunks <= 65535, "decode_attn: too many key chunks");
+  auto part = at::empty({nchunks, hq, d + 2}, q.options().dtype(at::kFloat));
+  auto o = at::empty({hq * d}, q.options());
+  FT_DISPATCH_E(q.scalar_type(), {
+    if (d == 64) launch_attn<E, 64>(q, k_cache, v_cache, part, o, (int)hq, (int)hkv, (int)n_keys, nchunks);
+    else launch_attn<E, 128>(q, k_cache, v_cache, part, o, (int)hq, (int)hkv, (int)n_keys, nchunks);
+  });
+  FT_LAUNCH_CHECK();
+  return o;
+}
+
+// Keys per workgroup of decode_attn (the tests place n_keys around its multiples).
+int64_t decode_attn_chunk() { return DECODE_CHUNK; }
+
+// out[r] = one token drawn from row r of logits [R, V]; a pure function of
+// (logits, temperature, top_k, key, step, r). temperature 0: the lowest column of the row maximum.
+void sample_(const at::Tensor& logits, const at::Tensor& out, double temperature, int64_t top_k, int64_t key,
+             int64_t step) {
+  FT_CHECK_CUDA(logits);
+  FT_CHECK_MODEL_DTYPE(logits);
+  FT_CHECK_CONTIG(logits);
+  FT_CHECK_CUDA(out);
+  FT_CHECK_CONTIG(out);
+  TORCH_CHECK(out.scalar_type() == at::kLong && out.device() == logits.device(), "sample_: out must be int64 on logits' device");
+  TORCH_CHECK(logits.dim() >= 1 && logits.size(-1) > 0, "sample_: logits must be [R, V]");
+  const int64_t V = logits.size(-1);
+  TORCH_CHECK(V % 8 == 0, "sample_: vocab must be a multiple of 8");
+  const int64_t R = logits.numel() / V;
+  TORCH_CHECK(V <= INT_MAX && R <= INT_MAX, "sample_: R and V must fit 32 bits");
+  TORCH_CHECK(out.numel() == R, "sample_: out shape mismatch");
+  TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY, "sample_: temperature must be finite and >= 0");
+  TORCH_CHECK(top_k >= 0, "sample_: top_k must be >= 0 (0: all columns)");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "sample_: logits must be 16-byte aligned");
+  const at::DeviceGuard guard(logits.device());
+  const uint64_t k64 = (uint64_t)key;
+  if (R > 0)
+    FT_DISPATCH_E(logits.scalar_type(),
+                  hipLaunchKernelGGL(sample_kernel<E>, dim3((unsigned)std::min<int64_t>(R, SAMPLE_MAX_BLOCKS)), dim3(256),
+                                     0, ft_stream(), cptr<typename E::T>(logits), mptr<int64_t>(out), (int)V, (int)R,
+                                     (float)temperature, (int)std::min<int64_t>(top_k, V), (uint32_t)k64,
+                                     (uint32_t)(k64 >> 32), (uint32_t)(uint64_t)step));
+  FT_LAUNCH_CHECK();
+}
+
+TORCH_LIBRARY_FRAGMENT(ftamd, m) {
+  m.def("gemv(Tensor x, Tensor w, Tensor? residual) -> Tensor", &gemv);
+  m.def("gemv_swiglu(Tensor x, Tensor w13) -> Tensor", &gemv_swiglu);
+  m.def("decode_qkv_append_(Tensor(a!) qkv, Tensor cos, Tensor sin, int pos, Tensor(b!) k_cache, "
+        "Tensor(c!) v_cache) -> ()",
+        &decode_qkv_append_);
+  m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, int n_keys) -> Tensor", &decode_attn);
+  m.def("decode_attn_chunk() -> int", &decode_attn_chunk);
+  m.def("sample_(Tensor logits, Tensor(a!) out, float temperature, int top_k, int key, int step) -> ()", &sample_);
+}

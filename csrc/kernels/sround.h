@@ -7,7 +7,8 @@
 //   The 16 random bits of an element depend on exactly (key, step, buffer, index):
 //     key    64-bit, (key_lo, key_hi) = (key & 0xffffffff, key >> 32)
 //     step   optimizer step number, taken mod 2^32
-//     buffer 0 params, 1 exp_avg, 2 exp_avg_sq
+//     buffer 0 params, 1 exp_avg, 2 exp_avg_sq (3: the token sampler's stream, decode.hip: index = row,
+//            step = the sampler's step, first word only -- no rounding involved)
 //     index  the element's global index in the flat layout, 64-bit
 //
 //   One generator call serves the 8 elements of vector c = index >> 3:
@@ -35,7 +36,7 @@
 #include "common.h"
 
 constexpr int SR_ROUNDS = 6;
-enum : uint32_t { SR_BUF_PARAM = 0, SR_BUF_EXP_AVG = 1, SR_BUF_EXP_AVG_SQ = 2 };
+enum : uint32_t { SR_BUF_PARAM = 0, SR_BUF_EXP_AVG = 1, SR_BUF_EXP_AVG_SQ = 2, SR_BUF_SAMPLE = 3 };
 
 // (key, step, offset) of a launch; c0 = offset / 8: the vector index of the launch's first vector.
 struct SrArgs {

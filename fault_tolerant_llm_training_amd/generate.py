@@ -1,0 +1,129 @@
+"""``python -m fault_tolerant_llm_training_amd.generate``: text from a training checkpoint.
+
+Loads only the ``model`` entry of the file (``ckpt.format.load_checkpoint`` maps the storages, so
+the AdamW moments are never read) into a model of the given preset (``ckpt.state.restore_model``,
+strict), generates with ``generation.generate`` and prints the decoded text; ``--json`` prints one
+line with the prompt ids, the generated ids, the text, the seconds and the tokens per second.
+A file that does not fit the model is reported as one error line and a non-zero exit code.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+
+import torch
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(prog="python -m fault_tolerant_llm_training_amd.generate", description=__doc__)
+    p.add_argument("--checkpoint", type=str, required=True, help="Checkpoint file written by train.py")
+    p.add_argument("--model", type=str, default="llama3-8b", help="Architecture preset, as in train.py")
+    p.add_argument("--vocab-size", type=int, default=0,
+                   help="Vocabulary size the model was trained with (0: the tokenizer's, as in train.py)")
+    p.add_argument("--tokenizer-name-or-path", type=str, default="unsloth/Mistral-Nemo-Base-2407-bnb-4bit",
+                   help="Tokenizer, as in train.py (`byte`: the built-in byte-level tokenizer)")
+    p.add_argument("--model-dtype", type=str, default="bf16", help="Model dtype (bf16/fp16/fp32/fp64)")
+    p.add_argument("--device", type=str, default="cuda", choices=["cuda", "cpu"])
+    p.add_argument("--sequence-length", type=int, default=0,
+                   help="Length of the RoPE tables and the longest prompt + generation (0: the checkpoint's)")
+    g = p.add_mutually_exclusive_group()
+    g.add_argument("--prompt", type=str, default=None, help="Prompt text (needs the tokenizer)")
+    g.add_argument("--prompt-ids", type=str, default=None, help="Prompt as comma-separated token ids, e.g. 1,2,3")
+    p.add_argument("--max-new-tokens", type=int, default=64)
+    p.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
+    p.add_argument("--top-k", type=int, default=0, help="0: all tokens")
+    p.add_argument("--seed", type=int, default=1234, help="Seed of the sampler key")
+    p.add_argument("--json", action="store_true", help="Print one JSON line instead of the text")
+    return p
+
+
+def _fail(msg: str) -> int:
+    print(f"generate: error: {msg}", file=sys.stderr, flush=True)
+    return 2
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    from .ckpt.format import load_checkpoint
+    from .ckpt.state import restore_model
+    from .generation import generate
+    from .models.llama import PRESETS, build_model, model_args_for
+    from .utils.config import PRECISION_STR_TO_DTYPE
+    from .utils.sround import key_from_seed
+
+    if args.model not in PRESETS:
+        return _fail(f"unknown --model {args.model!r}; choose from {sorted(PRESETS)}")
+    if args.model_dtype not in PRECISION_STR_TO_DTYPE:
+        return _fail(f"unknown --model-dtype {args.model_dtype!r}")
+    if args.max_new_tokens < 1 or args.temperature < 0 or args.top_k < 0:
+        return _fail("--max-new-tokens must be >= 1, --temperature and --top-k >= 0")
+    tok = None
+    if args.prompt_ids is None or not args.vocab_size:
+        from .data.tokenizer import load_tokenizer
+
+        try:
+            tok = load_tokenizer(args.tokenizer_name_or_path)
+        except Exception as e:  # noqa: BLE001 - reported as the one error line
+            return _fail(f"cannot load the tokenizer {args.tokenizer_name_or_path!r} ({e!r}); "
+                         "give --prompt-ids and --vocab-size to do without one")
+    try:
+        if args.prompt_ids is not None:
+            prompt = [int(s) for s in args.prompt_ids.split(",") if s.strip()]
+        elif args.prompt is not None:
+            from .data.tokenizer import encode
+
+            prompt = encode(tok, args.prompt)
+        else:
+            bos = getattr(tok, "bos_token_id", None)
+            prompt = [1 if bos is None else int(bos)]
+    except ValueError as e:
+        return _fail(f"--prompt-ids: {e}")
+    if not prompt:
+        return _fail("the prompt is empty")
+    vocab = args.vocab_size or int(tok.vocab_size)
+    try:
+        ckpt = load_checkpoint(args.checkpoint)
+    except Exception as e:  # noqa: BLE001
+        return _fail(f"cannot read {args.checkpoint}: {e!r}")
+    meta = ckpt.get("meta") or {}
+    seq_len = args.sequence_length or int((meta.get("model_args") or {}).get("seq_len", 0)) or 2048
+    device = torch.device(args.device)
+    dtype = PRECISION_STR_TO_DTYPE[args.model_dtype]
+    margs = model_args_for(args.model, vocab_size=vocab, seq_len=seq_len)
+    rec = meta.get("model_args") or {}
+    diff = [f"{f}: file {rec[f]!r}, --model {getattr(margs, f)!r}"
+            for f in ("dim", "n_layers", "n_heads", "n_kv_heads", "multiple_of", "ffn_dim_multiplier", "norm_type",
+                      "vocab_size") if f in rec and rec[f] != getattr(margs, f)]
+    if diff:  # before anything is allocated for the wrong architecture
+        return _fail(f"{args.checkpoint} does not fit --model {args.model} with vocabulary {vocab} ({'; '.join(diff)})")
+    try:
+        model = build_model(margs, device, dtype)
+        restore_model(model, ckpt["model"])
+    except Exception as e:  # noqa: BLE001 - a layout mismatch: keys, shapes or sizes
+        return _fail(f"{args.checkpoint} does not fit --model {args.model} with vocabulary {vocab}: "
+                     f"{type(e).__name__}: {str(e).splitlines()[0] if str(e) else ''}")
+    del ckpt
+    model.eval()
+    eos = getattr(tok, "eos_token_id", None) if tok is not None else None
+    if device.type == "cuda":
+        torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    try:
+        ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
+                       key=key_from_seed(args.seed), eos_id=eos)
+    except ValueError as e:
+        return _fail(str(e))
+    dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished
+    text = tok.decode(ids) if tok is not None else ""
+    if args.json:
+        print(json.dumps({"prompt_ids": prompt, "ids": ids, "text": text, "seconds": dt,
+                          "tokens_per_s": len(ids) / dt if dt > 0 else 0.0}), flush=True)
+    else:
+        print(text if tok is not None else ",".join(str(i) for i in ids), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

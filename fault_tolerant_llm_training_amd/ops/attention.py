@@ -273,6 +273,30 @@ def qkv_rope_attention(xn, wqkv, sink, cos, sin, seq_len, hq, hkv, d, keep: Opti
     return rope_attention(qkv.view(-1, qkv.shape[-1]), cos, sin, seq_len, hq, hkv, d, keep, gen, doc=doc)
 
 
+@torch.no_grad()
+def qkv_rope_attention_kv(xn, wqkv, cos, sin, seq_len, hq, hkv, d):
+    """:func:`qkv_rope_attention` for the prefill of text generation (forward only, plain causal
+    attention): the same projection, RoPE and flash forward on the same route, and besides o the
+    rotated K and the V of every row, ``[T, Hkv D]`` each, for the KV cache. On the QKV-epilogue
+    route the rotated K is a slice of ``qkv``, on the other one a slice of the RoPE kernel's output;
+    V is a slice of ``qkv`` on both."""
+    x2 = xn.reshape(-1, xn.shape[-1])
+    a, b = hq * d, (hq + hkv) * d
+    if not native(x2):
+        qkv = Fx.linear(xn, wqkv, None).view(x2.shape[0], -1)
+        B = x2.shape[0] // seq_len
+        k = rope_reference(qkv[:, a:b].reshape(B, seq_len, hkv, d), cos, sin).reshape(-1, hkv * d)
+        return attention_reference(qkv, cos, sin, seq_len, hq, hkv, d), k, qkv[:, b:]
+    if _qkv_rope_ok(x2, wqkv, d):
+        qkv = QKVRopeFn.apply(x2.contiguous(), wqkv, None, cos, sin, seq_len, hq, hkv, d)
+        qk = qkv
+    else:
+        qkv = Fx.linear(xn, wqkv, None).view(x2.shape[0], -1).contiguous()
+        qk = kernels().rope_fwd(qkv, cos, sin, seq_len, hq, hkv, d)
+    o, _ = flash_attn_fwd(qk, qkv, seq_len, hq, hkv, d)
+    return o, qk[:, a:b], qkv[:, b:]
+
+
 # functional.py re-exports this module's names at its end and this module calls into functional at
 # run time: imported last, so either module can be imported first
 from . import functional as Fx  # noqa: E402

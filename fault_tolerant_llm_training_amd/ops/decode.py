@@ -1,0 +1,83 @@
+"""One-row (decode) ops of text generation: wrappers of csrc/kernels/decode.hip.
+
+GPU tensors of a kernel dtype run the HIP kernels (``kernels()`` raises if the library is
+missing); CPU tensors and fp64 take the composed-PyTorch definition of the same math, as in
+``ops.functional``. ``generation.py`` is the caller.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+
+from .._native import kernels, native
+from .attention import rope_reference
+from .functional import swiglu_reference
+
+
+def _gemv_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """The kernel's preconditions: 16-byte vectors along K (K % 8, fp32: K % 4) of contiguous,
+    16-byte aligned operands. Anything else goes to ``torch.mv`` (the route ``f32_route`` leaves to
+    hipBLASLt for the same reason)."""
+    vn = 4 if w.dtype == torch.float32 else 8
+    return (native(w) and native(x) and x.dtype == w.dtype and w.dim() == 2 and x.dim() == 1
+            and w.shape[1] % vn == 0 and w.shape[1] > 0 and w.shape[0] > 0 and w.is_contiguous()
+            and x.is_contiguous() and w.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0)
+
+
+def gemv(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[N] = w[N, K] x[K] (+ residual[N])."""
+    if _gemv_ok(x, w):
+        return kernels().gemv(x, w, None if residual is None else residual.contiguous())
+    y = torch.mv(w, x)
+    return y if residual is None else y + residual
+
+
+def gemv_swiglu(x: torch.Tensor, w13: torch.Tensor) -> torch.Tensor:
+    """a[H] = silu(w1 x) * (w3 x) on the fused [w1; w3] view [2H, K]."""
+    if _gemv_ok(x, w13) and w13.shape[0] % 2 == 0:
+        return kernels().gemv_swiglu(x, w13)
+    return swiglu_reference(torch.mv(w13, x))
+
+
+def qkv_append_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: int, k_cache: torch.Tensor,
+                v_cache: torch.Tensor) -> None:
+    """RoPE at ``pos`` on Q (in place) and K (into ``k_cache[:, pos]``), V into ``v_cache[:, pos]``.
+    qkv: [(Hq + 2 Hkv) D]; caches: [Hkv, Smax, D]."""
+    if native(qkv):
+        kernels().decode_qkv_append_(qkv, cos, sin, int(pos), k_cache, v_cache)
+        return
+    hkv, _, d = k_cache.shape
+    hq = qkv.numel() // d - 2 * hkv
+    c, s = cos[pos : pos + 1], sin[pos : pos + 1]
+    qk = rope_reference(qkv[: (hq + hkv) * d].view(1, 1, hq + hkv, d), c, s).view(hq + hkv, d)
+    qkv[: hq * d] = qk[:hq].reshape(-1)
+    k_cache[:, pos] = qk[hq:]
+    v_cache[:, pos] = qkv[(hq + hkv) * d :].view(hkv, d)
+
+
+def attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_keys: int) -> torch.Tensor:
+    """o[Hq D]: one (rotated) query over keys ``0 .. n_keys - 1`` of the caches; GQA."""
+    if native(q):
+        return kernels().decode_attn(q, k_cache, v_cache, int(n_keys))
+    hkv, _, d = k_cache.shape
+    hq = q.numel() // d
+    k = k_cache[:, :n_keys].repeat_interleave(hq // hkv, dim=0)  # [Hq, n, D]
+    v = v_cache[:, :n_keys].repeat_interleave(hq // hkv, dim=0)
+    s = torch.einsum("hd,hnd->hn", q.view(hq, d), k) / math.sqrt(d)
+    return torch.einsum("hn,hnd->hd", F.softmax(s, dim=-1), v).reshape(-1)
+
+
+def sample(logits: torch.Tensor, temperature: float, top_k: int, key: int, step: int) -> torch.Tensor:
+    """One token per row of ``logits`` ([V] or [R, V]): int64 tensor [R] on ``logits``' device.
+    The definition is ``utils.sampling.sample_reference``."""
+    x2 = logits.reshape(-1, logits.shape[-1])
+    if native(x2) and x2.shape[1] % 8 == 0:
+        out = torch.empty(x2.shape[0], dtype=torch.int64, device=x2.device)
+        kernels().sample_(x2.contiguous(), out, float(temperature), int(top_k), int(key), int(step))
+        return out
+    from ..utils.sampling import sample_reference
+
+    return sample_reference(x2, temperature, top_k, key, step).to(x2.device)

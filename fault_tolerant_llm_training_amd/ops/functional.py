@@ -798,6 +798,7 @@ from .attention import (  # noqa: E402,F401
     attention_reference,
     doc_bounds,
     qkv_rope_attention,
+    qkv_rope_attention_kv,
     rope_attention,
     rope_reference,
     set_qkv_rope,

@@ -671,6 +671,55 @@ def train(args) -> int:
                 metrics_f.write(json.dumps(tensor_stats.metrics_record(step_now, rec)) + "\n")
                 metrics_f.flush()
 
+    sample_every = int(getattr(args, "sample_every", 0) or 0)
+    sample_prompt, sample_tok = None, None
+    if sample_every > 0:
+        from . import generation
+        from .utils.sround import key_from_seed
+
+        if args.synthetic_data:
+            sample_prompt = [holder["bos"]]  # no tokenizer: the BOS id alone, ids are printed
+        else:
+            from .data.tokenizer import encode, load_tokenizer
+
+            sample_tok = load_tokenizer(args.tokenizer_name_or_path)
+            sample_prompt = [holder["bos"]] if args.sample_prompt is None else encode(sample_tok, args.sample_prompt)
+        if not sample_prompt or len(sample_prompt) + args.sample_tokens > S:
+            raise ValueError(f"--sample-every: prompt ({len(sample_prompt)} tokens) + --sample-tokens "
+                             f"({args.sample_tokens}) exceed --sequence-length ({S})")
+        sample_key = key_from_seed(args.seed)
+        logger.info(f"Sampling: every {sample_every} steps and after the last step -- rank 0 generates "
+                    f"{args.sample_tokens} tokens from a prompt of {len(sample_prompt)} (temperature "
+                    f"{args.sample_temperature:g}, top-k {args.sample_top_k}; key {sample_key:#018x} from --seed, "
+                    "sampler step = training step); the other ranks wait in the next vote (keep it far below "
+                    "--peer-timeout)")
+
+    def sample_at(step_now: int) -> None:
+        """--sample-every: one generated sample at step boundary ``step_now``, after the vote, a periodic
+        save, an evaluation and the statistics. Rank 0 alone: the parameters are replicated (ZeRO-1: after
+        the all-gather the gate waits for) and generation issues no collective. Read-only."""
+        complete_pending()  # graph mode: the parameters of this boundary exist after the pending optimizer step
+        if not info.is_main:
+            return
+        nonlocal pending_err
+        t0 = time.perf_counter()
+        try:
+            ids = generation.generate(model, sample_prompt, args.sample_tokens, temperature=args.sample_temperature,
+                                      top_k=args.sample_top_k, key=sample_key, step=step_now,
+                                      eos_id=getattr(sample_tok, "eos_token_id", None))
+        except Exception as e:  # noqa: BLE001 - becomes this rank's vote: every rank stops at the next boundary
+            logger.error(f"Sample error at step {step_now}: {e!r}")
+            if pending_err is None:
+                pending_err = e
+            return
+        dt = time.perf_counter() - t0
+        text = sample_tok.decode(ids) if sample_tok is not None else " ".join(str(i) for i in ids)
+        logger.info(f"Sample at step {step_now} | {text!r} | {len(ids)} tokens | {dt:.2f} s")
+        if metrics_f is not None:
+            metrics_f.write(json.dumps({"sample_step": step_now, "sample_ids": ids, "sample_text": text,
+                                        "sample_s": dt}) + "\n")
+            metrics_f.flush()
+
     emb_dim = margs.dim
     exit_code = 0
 
@@ -739,6 +788,8 @@ def train(args) -> int:
                 evaluate_at(training_step)
             if tstats is not None and tensor_stats.should_record(training_step, stats_every, first_boundary):
                 tensor_stats_at(training_step)
+            if sample_every > 0 and training_step > 0 and training_step % sample_every == 0:
+                sample_at(training_step)
 
             if prof_range is not None and training_step == prof_range[0] and prof is None:
                 acts = [torch.profiler.ProfilerActivity.CPU]
@@ -864,6 +915,8 @@ def train(args) -> int:
             evaluate_at(training_step, final=True)
         if tstats is not None and tensor_stats.should_record(training_step, stats_every, first_boundary):
             tensor_stats_at(training_step)
+        if sample_every > 0:
+            sample_at(training_step)
         if ckpt["engine"] is not None:
             ckpt["engine"].wait()
         log_digest(training_step)

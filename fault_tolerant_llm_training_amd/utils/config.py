@@ -304,6 +304,37 @@ def build_parser() -> argparse.ArgumentParser:
         "the parameters whose gradient holds NaN / Inf (0: off)",
     )
     parser.add_argument(
+        "--sample-every",
+        type=int,
+        default=0,
+        help="Generate a text sample every N steps (at each step boundary with training_step %% N == 0 and "
+        "training_step > 0) and once more after the last step, after a periodic save, an evaluation and the "
+        "tensor statistics: rank 0 alone decodes --sample-tokens tokens from --sample-prompt with the KV-cache "
+        "kernels; a read-only pass that leaves the training state untouched bit for bit (0: off). The other "
+        "ranks wait in the next vote, so a sample has to stay far below --peer-timeout",
+    )
+    parser.add_argument(
+        "--sample-prompt",
+        type=str,
+        default=None,
+        help="Prompt of --sample-every (default: the BOS token alone); needs the tokenizer, so not with "
+        "--synthetic-data",
+    )
+    parser.add_argument(
+        "--sample-tokens",
+        type=int,
+        default=64,
+        help="Tokens generated per sample (1 .. 1024; prompt + tokens may not exceed --sequence-length)",
+    )
+    parser.add_argument(
+        "--sample-temperature",
+        type=float,
+        default=0.0,
+        help="Sampling temperature of --sample-every (0: greedy). The sampler is stateless: its key comes from "
+        "--seed and its step is the training step, so a resumed chain prints the sample an uninterrupted run prints",
+    )
+    parser.add_argument("--sample-top-k", type=int, default=0, help="Top-k of --sample-every (0: all tokens)")
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -336,6 +367,21 @@ def get_args(argv=None) -> argparse.Namespace:
         parser.error(f"--eval-every must be >= 0, got {args.eval_every}")
     if args.tensor_stats_every < 0:
         parser.error(f"--tensor-stats-every must be >= 0, got {args.tensor_stats_every}")
+    if args.sample_every < 0:
+        parser.error(f"--sample-every must be >= 0, got {args.sample_every}")
+    if args.sample_every > 0:
+        if not 1 <= args.sample_tokens <= 1024:
+            parser.error(f"--sample-tokens must be in 1 .. 1024, got {args.sample_tokens}")
+        if args.sample_temperature < 0 or args.sample_top_k < 0:
+            parser.error("--sample-temperature and --sample-top-k must be >= 0")
+        if args.sample_prompt is not None and args.synthetic_data:
+            parser.error("--sample-prompt needs the tokenizer: not with --synthetic-data (the default prompt, "
+                         "the BOS token alone, needs none)")
+        # a text prompt is counted in tokens once the tokenizer is loaded (trainer.py); the BOS-only
+        # default is one token
+        if 1 + args.sample_tokens > args.sequence_length:
+            parser.error(f"--sample-every: prompt (1 token) + --sample-tokens ({args.sample_tokens}) exceed "
+                         f"--sequence-length ({args.sequence_length})")
     if args.eval_every > 0:
         if not args.eval_dataset and not args.synthetic_data:
             parser.error("--eval-every needs a held-out set: give --eval-dataset (only --synthetic-data runs "

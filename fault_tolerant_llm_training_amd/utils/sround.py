@@ -20,6 +20,7 @@ import torch
 
 ROUNDS = 6
 BUF_PARAM, BUF_EXP_AVG, BUF_EXP_AVG_SQ = 0, 1, 2
+BUF_SAMPLE = 3  # the token sampler's stream (utils/sampling.py; csrc/kernels/decode.hip)
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
