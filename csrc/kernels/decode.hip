@@ -13,12 +13,18 @@
 //   decode_attn         one query over keys 0 .. n_keys-1 of the cache, GQA indexed in place
 //   sample_             one token per row of logits: greedy, or temperature / top-k sampling
 //
+// Batched generation (B sequences per pass over the weights) has a `_rows` form of the first four:
+// gemv_rows, gemv_swiglu_rows, decode_qkv_append_rows_, decode_attn_rows. Each returns for row r the
+// bits the one-row op returns for that row alone: the per-row arithmetic is shared code (dotf,
+// qkv_append_vec, attn_chunk, attn_merge) run in the same order.
+//
 // Reproducibility: nothing on a result path is accumulated with atomics and every reduction has a
 // fixed order (per-lane sweep, xor butterfly over the wave, waves in index order, key chunks in
 // chunk order), so each op returns the same bits from run to run. The sampler's top-k threshold is
 // found with integer histograms in LDS (integer counts do not depend on the order of the adds).
 //
-// Positions, key counts and the sampler's step are host integers (kernel arguments).
+// Positions, key counts and the sampler's step are host integers (kernel arguments); the `_rows` ops
+// take each row's start position from a device tensor `pos0` plus one host integer `t`.
 #include <climits>
 
 #include "sround.h"
@@ -55,13 +61,18 @@ __device__ __forceinline__ void unpv(const uint4& v, float* f) {
 // fp32 accumulator; x comes from the cache (every wave reads the same K elements). The lane sums
 // are added as (a0 + a1) + (a2 + a3), then the xor butterfly over the wave.
 // --------------------------------------------------------------------------------------------
+template <int VN>
+__device__ __forceinline__ float dotf(const float* wf, const float* xf, float acc) {
+#pragma unroll
+  for (int j = 0; j < VN; ++j) acc = fmaf(wf[j], xf[j], acc);
+  return acc;
+}
+
 template <class E, int VN>
 __device__ __forceinline__ float dotv(const uint4& wv, const float* xf, float acc) {
   float wf[8];
   unpv<E>(wv, wf);
-#pragma unroll
-  for (int j = 0; j < VN; ++j) acc = fmaf(wf[j], xf[j], acc);
-  return acc;
+  return dotf<VN>(wf, xf, acc);
 }
 
 template <class E, bool SWIGLU>
@@ -116,18 +127,99 @@ __global__ __launch_bounds__(256) void gemv_kernel(const typename E::T* __restri
 }
 
 // --------------------------------------------------------------------------------------------
+// gemv_rows / gemv_swiglu_rows: x [R, K]. The wave of gemv_kernel, with every 16-byte weight vector
+// used for a tile of RT activation rows r0 .. r0 + RT - 1 (r0 = tile * RT); per activation row the
+// accumulators a[r][u], the k each of them sees, the tail into a[r][0] and the final adds are those
+// of gemv_kernel, so y[r] has the bits of gemv on x[r]. Rows of the tile at and beyond R are computed
+// on row R - 1 again and not stored (no divergence in the sweep). The tiles of one block of output
+// rows are neighbours in the grid, so the tiles after the first find the weights in a cache.
+// --------------------------------------------------------------------------------------------
+template <class E, bool SWIGLU, int RT>
+__global__ __launch_bounds__(256) void gemv_rows_kernel(const typename E::T* __restrict__ x,
+                                                        const typename E::T* __restrict__ w,
+                                                        const typename E::T* __restrict__ res,
+                                                        typename E::T* __restrict__ y, int N, int K, int R,
+                                                        int ntiles) {
+  constexpr int VN = V16<E>::N;
+  constexpr int STEP = 64 * VN;
+  const int lane = threadIdx.x & 63;
+  const int tile = blockIdx.x % ntiles;
+  const int row = (blockIdx.x / ntiles) * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;  // whole waves leave; the kernel has no block barrier
+  const int r0 = tile * RT;
+  const typename E::T* w0 = w + (long)row * K;
+  const typename E::T* w1 = w + ((long)row + N) * K;  // SWIGLU only: the w3 row of feature `row`
+  const typename E::T* xr[RT];
+  float a[RT][4], b[RT][4];
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    xr[r] = x + (long)min(r0 + r, R - 1) * K;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) a[r][u] = b[r][u] = 0.f;
+  }
+  int k = lane * VN;
+  for (; k + 3 * STEP < K; k += 4 * STEP) {
+    uint4 wv[4], uv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      wv[u] = *reinterpret_cast<const uint4*>(w0 + k + u * STEP);
+      if constexpr (SWIGLU) uv[u] = *reinterpret_cast<const uint4*>(w1 + k + u * STEP);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float wf[8], uf[8];
+      unpv<E>(wv[u], wf);
+      if constexpr (SWIGLU) unpv<E>(uv[u], uf);
+#pragma unroll
+      for (int r = 0; r < RT; ++r) {
+        float xf[8];
+        unpv<E>(*reinterpret_cast<const uint4*>(xr[r] + k + u * STEP), xf);
+        a[r][u] = dotf<VN>(wf, xf, a[r][u]);
+        if constexpr (SWIGLU) b[r][u] = dotf<VN>(uf, xf, b[r][u]);
+      }
+    }
+  }
+  for (; k < K; k += STEP) {
+    float wf[8], uf[8];
+    unpv<E>(*reinterpret_cast<const uint4*>(w0 + k), wf);
+    if constexpr (SWIGLU) unpv<E>(*reinterpret_cast<const uint4*>(w1 + k), uf);
+#pragma unroll
+    for (int r = 0; r < RT; ++r) {
+      float xf[8];
+      unpv<E>(*reinterpret_cast<const uint4*>(xr[r] + k), xf);
+      a[r][0] = dotf<VN>(wf, xf, a[r][0]);
+      if constexpr (SWIGLU) b[r][0] = dotf<VN>(uf, xf, b[r][0]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < RT; ++r) {
+    float s = wave_sum((a[r][0] + a[r][1]) + (a[r][2] + a[r][3]));
+    const bool store = lane == 0 && r0 + r < R;
+    const long at = (long)(r0 + r) * N + row;
+    if constexpr (SWIGLU) {
+      const float t = wave_sum((b[r][0] + b[r][1]) + (b[r][2] + b[r][3]));
+      if (store) {
+        // g, u and silu(g) each rounded to the model dtype, as in gemv_kernel
+        const float g = rnd<E>(s), u = rnd<E>(t);
+        const float sl = rnd<E>(g / (1.f + expf(-g)));
+        y[at] = cvt1<E>(sl * u);
+      }
+    } else if (store) {
+      if (res != nullptr) s += ld1<E>(res + at);
+      y[at] = cvt1<E>(s);
+    }
+  }
+}
+
+// --------------------------------------------------------------------------------------------
 // decode_qkv_append_: qkv [(Hq + 2 Hkv) D] of the new token. One thread per 8 columns (4 pairs).
 // --------------------------------------------------------------------------------------------
 template <class E>
-__global__ __launch_bounds__(256) void qkv_append_kernel(typename E::T* __restrict__ qkv,
-                                                         const float* __restrict__ cos_row,
-                                                         const float* __restrict__ sin_row,
-                                                         typename E::T* __restrict__ kc,
-                                                         typename E::T* __restrict__ vc, int hq, int hkv, int d,
-                                                         long smax, long pos) {
-  const int nvec = (hq + 2 * hkv) * d / 8;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nvec) return;
+__device__ __forceinline__ void qkv_append_vec(int i, typename E::T* __restrict__ qkv,
+                                               const float* __restrict__ cos_row,
+                                               const float* __restrict__ sin_row, typename E::T* __restrict__ kc,
+                                               typename E::T* __restrict__ vc, int hq, int hkv, int d, long smax,
+                                               long pos) {
   const int col = i * 8, head = col / d, within = col - head * d;
   float x[8];
   ld8<E>(qkv + col, x);
@@ -149,19 +241,56 @@ __global__ __launch_bounds__(256) void qkv_append_kernel(typename E::T* __restri
   }
 }
 
+template <class E>
+__global__ __launch_bounds__(256) void qkv_append_kernel(typename E::T* __restrict__ qkv,
+                                                         const float* __restrict__ cos_row,
+                                                         const float* __restrict__ sin_row,
+                                                         typename E::T* __restrict__ kc,
+                                                         typename E::T* __restrict__ vc, int hq, int hkv, int d,
+                                                         long smax, long pos) {
+  const int nvec = (hq + 2 * hkv) * d / 8;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nvec) return;
+  qkv_append_vec<E>(i, qkv, cos_row, sin_row, kc, vc, hq, hkv, d, smax, pos);
+}
+
+// decode_qkv_append_rows_: qkv [B, (Hq + 2 Hkv) D], caches [B, Hkv, Smax, D]; blockIdx.y is the row b,
+// rotated and stored at pos0[b] + t. A position outside [0, limit) -- the host checked the largest one
+// the caller named, not pos0 itself -- writes nothing.
+template <class E>
+__global__ __launch_bounds__(256) void qkv_append_rows_kernel(typename E::T* __restrict__ qkv,
+                                                              const float* __restrict__ cos_t,
+                                                              const float* __restrict__ sin_t,
+                                                              const int* __restrict__ pos0, int t,
+                                                              typename E::T* __restrict__ kc,
+                                                              typename E::T* __restrict__ vc, int hq, int hkv,
+                                                              int d, long smax, long limit) {
+  const int nvec = (hq + 2 * hkv) * d / 8;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  const long pos = (long)pos0[b] + t;
+  if (i >= nvec || pos < 0 || pos >= limit) return;
+  const long cstride = (long)hkv * smax * d;
+  qkv_append_vec<E>(i, qkv + (long)b * nvec * 8, cos_t + pos * (d / 2), sin_t + pos * (d / 2), kc + b * cstride,
+                    vc + b * cstride, hq, hkv, d, smax, pos);
+}
+
 // --------------------------------------------------------------------------------------------
 // decode_attn. Workgroup (kv head, chunk of DECODE_CHUNK keys), 256 threads. D / 8 lanes share a key
 // row (16 bytes of it each), so a pass covers 256 / (D / 8) keys; every K and V row is loaded once
 // and used for all the G = Hq / Hkv query heads of the group (in tiles of GT heads: one tile for
 // G <= 8). Per head the workgroup leaves (acc[D] unnormalised, m, l) of its chunk; the merge
 // kernel folds the chunks in chunk order. Keys at and beyond n_keys are never loaded.
+//
+// attn_chunk is the workgroup's work on one sequence (q [Hq D], caches [Hkv, Smax, D], part
+// [chunks, Hq, D + 2]); decode_attn_kernel runs it on the one sequence, decode_attn_rows_kernel on
+// sequence blockIdx.z of a batch.
 // --------------------------------------------------------------------------------------------
 template <class E, int D, int GT>
-__global__ __launch_bounds__(256) void decode_attn_kernel(const typename E::T* __restrict__ q,
-                                                          const typename E::T* __restrict__ kc,
-                                                          const typename E::T* __restrict__ vc,
-                                                          float* __restrict__ part, int hq, int hkv, long smax,
-                                                          int n_keys, float scale) {
+__device__ __forceinline__ void attn_chunk(const typename E::T* __restrict__ q,
+                                           const typename E::T* __restrict__ kc,
+                                           const typename E::T* __restrict__ vc, float* __restrict__ part,
+                                           int hq, int hkv, long smax, int n_keys, float scale) {
   constexpr int LPK = D / 8;     // lanes per key row
   constexpr int KPP = 256 / LPK;  // keys per pass
   __shared__ float sq[GT * D];
@@ -258,11 +387,45 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const typename E::T* _
   }
 }
 
+template <class E, int D, int GT>
+__global__ __launch_bounds__(256) void decode_attn_kernel(const typename E::T* __restrict__ q,
+                                                          const typename E::T* __restrict__ kc,
+                                                          const typename E::T* __restrict__ vc,
+                                                          float* __restrict__ part, int hq, int hkv, long smax,
+                                                          int n_keys, float scale) {
+  attn_chunk<E, D, GT>(q, kc, vc, part, hq, hkv, smax, n_keys, scale);
+}
+
+// The key count of row b of a batch: pos0[b] + t + 1, at most max_keys (which the host checked
+// against Smax; pos0 itself is never read back). Below 1 no workgroup of the row does anything.
+__device__ __forceinline__ int row_keys(const int* __restrict__ pos0, int b, int t, int max_keys) {
+  return (int)min((long)pos0[b] + t + 1, (long)max_keys);
+}
+
+// Grid (Hkv, ceil(max_keys / DECODE_CHUNK), B); q rows q_stride elements apart (the Q columns of a
+// qkv buffer, in place); part [B, gridDim.y, Hq, D + 2]. A workgroup whose chunk
+// starts at or beyond its row's key count leaves here, all of it, before the first barrier: its
+// slice of `part` stays unwritten and the merge below never reads it.
+template <class E, int D, int GT>
+__global__ __launch_bounds__(256) void decode_attn_rows_kernel(const typename E::T* __restrict__ q,
+                                                               const typename E::T* __restrict__ kc,
+                                                               const typename E::T* __restrict__ vc,
+                                                               float* __restrict__ part,
+                                                               const int* __restrict__ pos0, int t, int max_keys,
+                                                               long q_stride, int hq, int hkv, long smax,
+                                                               float scale) {
+  const int b = blockIdx.z;
+  const int n_keys = row_keys(pos0, b, t, max_keys);
+  if ((int)blockIdx.y * DECODE_CHUNK >= n_keys) return;  // uniform over the workgroup
+  const long cstride = (long)hkv * smax * D;
+  attn_chunk<E, D, GT>(q + b * q_stride, kc + b * cstride, vc + b * cstride,
+                       part + (long)b * gridDim.y * hq * (D + 2), hq, hkv, smax, n_keys, scale);
+}
+
 // One workgroup per query head, one thread per dim: the chunk partials in chunk order.
 template <class E, int D>
-__global__ __launch_bounds__(D) void decode_attn_merge_kernel(const float* __restrict__ part,
-                                                              typename E::T* __restrict__ o, int hq,
-                                                              int nchunks) {
+__device__ __forceinline__ void attn_merge(const float* __restrict__ part, typename E::T* __restrict__ o, int hq,
+                                           int nchunks) {
   const int h = blockIdx.x, dd = threadIdx.x;
   float M = -INFINITY, L = 0.f, A = 0.f;
   for (int c = 0; c < nchunks; ++c) {
@@ -275,6 +438,25 @@ __global__ __launch_bounds__(D) void decode_attn_merge_kernel(const float* __res
     M = nM;
   }
   o[(long)h * D + dd] = cvt1<E>(A / L);
+}
+
+template <class E, int D>
+__global__ __launch_bounds__(D) void decode_attn_merge_kernel(const float* __restrict__ part,
+                                                              typename E::T* __restrict__ o, int hq,
+                                                              int nchunks) {
+  attn_merge<E, D>(part, o, hq, nchunks);
+}
+
+// Grid (Hq, B): row b folds its own ceil(keys / DECODE_CHUNK) chunks of part [B, max_chunks, Hq, D + 2].
+template <class E, int D>
+__global__ __launch_bounds__(D) void decode_attn_merge_rows_kernel(const float* __restrict__ part,
+                                                                   typename E::T* __restrict__ o,
+                                                                   const int* __restrict__ pos0, int t,
+                                                                   int max_keys, int max_chunks, int hq) {
+  const int b = blockIdx.y;
+  const int n_keys = max(row_keys(pos0, b, t, max_keys), 0);
+  attn_merge<E, D>(part + (long)b * max_chunks * hq * (D + 2), o + (long)b * hq * D, hq,
+                   (n_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -552,6 +734,56 @@ at::Tensor gemv_impl(const char* op, const at::Tensor& x, const at::Tensor& w,
   return y;
 }
 
+// The tile heights of gemv_rows_kernel. R <= 8 takes the smallest tile that holds it; above, tiles
+// of GEMV_ROWS_TILE (SWIGLU: GEMV_SWIGLU_ROWS_TILE) rows.
+constexpr int GEMV_ROWS_TILE = 8;
+constexpr int GEMV_SWIGLU_ROWS_TILE = 8;
+
+template <bool SWIGLU>
+at::Tensor gemv_rows_impl(const char* op, const at::Tensor& x, const at::Tensor& w,
+                          const c10::optional<at::Tensor>& residual) {
+  FT_CHECK_MODEL_DTYPE(w);
+  check_vec(op, x, "x");
+  check_vec(op, w, "w");
+  TORCH_CHECK(x.scalar_type() == w.scalar_type() && x.device() == w.device(), op, ": x / w dtype or device mismatch");
+  TORCH_CHECK(w.dim() == 2 && x.dim() == 2 && x.size(1) == w.size(1), op, ": x [R, K], w [N, K]");
+  const int64_t R = x.size(0), rows = w.size(0), K = w.size(1);
+  const int vn = w.scalar_type() == at::kFloat ? 4 : 8;
+  TORCH_CHECK(K > 0 && K % vn == 0, op, ": K must be a positive multiple of ", vn, " (16-byte row vectors)");
+  TORCH_CHECK(R >= 1 && R <= INT_MAX, op, ": x needs at least one row");
+  TORCH_CHECK(rows > 0 && rows <= INT_MAX && K <= INT_MAX, op, ": N and K must fit 32 bits");
+  TORCH_CHECK(!SWIGLU || rows % 2 == 0, op, ": w13 must be [2H, K]");
+  const int64_t N = SWIGLU ? rows / 2 : rows;
+  const bool has_res = residual.has_value() && residual->defined();
+  if (has_res) {
+    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() && residual->scalar_type() == w.scalar_type() &&
+                    residual->device() == w.device() && residual->dim() == 2 && residual->size(0) == R &&
+                    residual->size(1) == N,
+                op, ": residual must be a contiguous [R, N] tensor of w's dtype and device");
+  }
+  constexpr int TOP = SWIGLU ? GEMV_SWIGLU_ROWS_TILE : GEMV_ROWS_TILE;
+  const int rt = R == 1 ? 1 : R == 2 ? 2 : (R <= 4 || TOP == 4) ? 4 : 8;
+  const int64_t ntiles = (R + rt - 1) / rt;
+  const int64_t blocks = (N + 3) / 4 * ntiles;
+  TORCH_CHECK(blocks <= INT_MAX, op, ": too many workgroups (N / 4 x row tiles)");
+  const at::DeviceGuard guard(w.device());
+  auto y = at::empty({R, N}, w.options());
+#define FT_GEMV_ROWS(RT)                                                                                       \
+  hipLaunchKernelGGL((gemv_rows_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(256), 0, ft_stream(),     \
+                     cptr<typename E::T>(x), cptr<typename E::T>(w),                                           \
+                     has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y), (int)N, (int)K, \
+                     (int)R, (int)ntiles)
+  FT_DISPATCH_E(w.scalar_type(), {
+    if (rt == 1) FT_GEMV_ROWS(1);
+    else if (rt == 2) FT_GEMV_ROWS(2);
+    else if (rt == 4) FT_GEMV_ROWS(4);
+    else FT_GEMV_ROWS(TOP);
+  });
+#undef FT_GEMV_ROWS
+  FT_LAUNCH_CHECK();
+  return y;
+}
+
 void check_cache(const char* op, const at::Tensor& c, const at::Tensor& like, int64_t hkv, int64_t d) {
   TORCH_CHECK(c.is_cuda() && c.device() == like.device() && c.scalar_type() == like.scalar_type(), op,
               ": the caches must be on qkv's device, in its dtype");
@@ -580,7 +812,124 @@ void launch_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc
                      mptr<typename E::T>(o), hq, nchunks);
 }
 
+template <class E, int D>
+void launch_attn_rows(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& part,
+                      const at::Tensor& o, const at::Tensor& pos0, int t, int max_keys, int max_chunks, int B,
+                      int hq, int hkv) {
+  const int G = hq / hkv;
+  const dim3 grid(hkv, max_chunks, B);
+  const float scale = 1.f / sqrtf((float)D);
+  const long smax = kc.size(2);
+#define FT_ATTN(GT)                                                                                             \
+  hipLaunchKernelGGL((decode_attn_rows_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(), cptr<typename E::T>(q), \
+                     cptr<typename E::T>(kc), cptr<typename E::T>(vc), mptr<float>(part), cptr<int>(pos0), t,   \
+                     max_keys, (long)q.stride(0), hq, hkv, smax, scale)
+  if (G == 1) FT_ATTN(1);
+  else if (G == 2) FT_ATTN(2);
+  else if (G <= 4) FT_ATTN(4);
+  else FT_ATTN(8);
+#undef FT_ATTN
+  FT_LAUNCH_CHECK();
+  hipLaunchKernelGGL((decode_attn_merge_rows_kernel<E, D>), dim3(hq, B), dim3(D), 0, ft_stream(), cptr<float>(part),
+                     mptr<typename E::T>(o), cptr<int>(pos0), t, max_keys, max_chunks, hq);
+}
+
+// The operands the two batched cache ops share: caches [B, Hkv, Smax, D] of x's dtype, pos0 int32 [B].
+void check_rows(const char* op, const at::Tensor& x, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                const at::Tensor& pos0) {
+  FT_CHECK_MODEL_DTYPE(x);
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.size(0) >= 1, op, ": the activation is a GPU tensor [B, width], B >= 1");
+  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) >= x.size(1) && x.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              op, ": the activation's rows must be dense, 16-byte aligned, a multiple of 8 elements apart");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == x.size(0), op, ": a cache is [B, Hkv, Smax, D]");
+  for (const at::Tensor* c : {&k_cache, &v_cache}) {
+    TORCH_CHECK(c->is_cuda() && c->device() == x.device() && c->scalar_type() == x.scalar_type(), op,
+                ": the caches must be on the activation's device, in its dtype");
+    TORCH_CHECK(c->is_contiguous() && c->sizes() == k_cache.sizes(), op,
+                ": the caches are contiguous [B, Hkv, Smax, D] tensors of one shape");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": a cache must be 16-byte aligned");
+  }
+  TORCH_CHECK(pos0.is_cuda() && pos0.device() == x.device() && pos0.scalar_type() == at::kInt &&
+                  pos0.is_contiguous() && pos0.dim() == 1 && pos0.size(0) == x.size(0),
+              op, ": pos0 must be a contiguous int32 [B] tensor on the activation's device");
+  TORCH_CHECK(x.size(0) <= 65535 && k_cache.size(2) <= INT_MAX, op, ": B or Smax too large");
+}
+
 }  // namespace
+
+// y[R, N] = x[R, K] w[N, K]^T (+ residual[R, N]); row r has the bits of gemv(x[r], w, residual[r]).
+at::Tensor gemv_rows(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
+  return gemv_rows_impl<false>("gemv_rows", x, w, residual);
+}
+
+// a[R, H]: row r has the bits of gemv_swiglu(x[r], w13).
+at::Tensor gemv_swiglu_rows(const at::Tensor& x, const at::Tensor& w13) {
+  return gemv_rows_impl<true>("gemv_swiglu_rows", x, w13, c10::nullopt);
+}
+
+// decode_qkv_append_ on row b of qkv [B, (hq + 2 hkv) d] at position pos0[b] + t of caches
+// [B, hkv, Smax, d]. max_pos is the caller's largest pos0[b] + t: the op checks it against Smax and
+// the RoPE tables and does not read pos0 back (a row beyond max_pos is left unwritten).
+void decode_qkv_append_rows_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
+                             const at::Tensor& pos0, int64_t t, int64_t max_pos, const at::Tensor& k_cache,
+                             const at::Tensor& v_cache) {
+  const char* op = "decode_qkv_append_rows_";
+  check_rows(op, qkv, k_cache, v_cache, pos0);
+  TORCH_CHECK(qkv.is_contiguous(), op, ": qkv must be contiguous");
+  const int64_t B = qkv.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
+  TORCH_CHECK(d > 0 && d % 8 == 0, op, ": head_dim must be a multiple of 8");
+  TORCH_CHECK(qkv.size(1) % d == 0 && qkv.size(1) / d > 2 * hkv, op, ": qkv width");
+  const int64_t hq = qkv.size(1) / d - 2 * hkv;
+  TORCH_CHECK(t >= 0 && t <= INT_MAX && max_pos >= t && max_pos < smax, op, ": largest position ", max_pos,
+              " (t = ", t, ") outside the cache [0, ", smax, ")");
+  for (const at::Tensor* c : {&cos_t, &sin_t}) {
+    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() && c->scalar_type() == at::kFloat && c->is_contiguous() &&
+                    c->dim() == 2 && c->size(1) == d / 2 && c->size(0) > max_pos,
+                op, ": cos / sin must be fp32 [S > largest position, D / 2] on qkv's device");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": cos / sin alignment");
+  }
+  const at::DeviceGuard guard(qkv.device());
+  const int nvec = (int)(qkv.size(1) / 8);
+  FT_DISPATCH_E(qkv.scalar_type(),
+                hipLaunchKernelGGL(qkv_append_rows_kernel<E>, dim3((nvec + 255) / 256, (unsigned)B), dim3(256), 0,
+                                   ft_stream(), mptr<typename E::T>(qkv), cptr<float>(cos_t), cptr<float>(sin_t),
+                                   cptr<int>(pos0), (int)t, mptr<typename E::T>(k_cache),
+                                   mptr<typename E::T>(v_cache), (int)hq, (int)hkv, (int)d, (long)smax,
+                                   (long)(max_pos + 1)));
+  FT_LAUNCH_CHECK();
+}
+
+// o[B, hq d]: q [B, hq d] may be a column slice of a wider buffer (rows stride(0) apart); row b is
+// decode_attn of q[b] over keys 0 .. pos0[b] + t of its caches [B, hkv, Smax, d],
+// bit for bit. max_keys is the caller's largest key count (pos0 is not read back).
+at::Tensor decode_attn_rows(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                            const at::Tensor& pos0, int64_t t, int64_t max_keys) {
+  const char* op = "decode_attn_rows";
+  check_rows(op, q, k_cache, v_cache, pos0);
+  const int64_t B = q.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
+  TORCH_CHECK(d == 64 || d == 128, op, ": head_dim must be 64 or 128");
+  TORCH_CHECK(q.size(1) % d == 0, op, ": q width");
+  const int64_t hq = q.size(1) / d;
+  TORCH_CHECK(hq > 0 && hq % hkv == 0, op, ": Hq must be a multiple of Hkv");
+  TORCH_CHECK(t >= 0 && t <= INT_MAX && max_keys > t && max_keys <= smax, op, ": max_keys ", max_keys, " (t = ", t,
+              ") outside [t + 1, Smax = ", smax, "]");
+  const at::DeviceGuard guard(q.device());
+  const int max_chunks = (int)((max_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
+  TORCH_CHECK(max_chunks <= 65535, op, ": too many key chunks");
+  auto part = at::empty({B, max_chunks, hq, d + 2}, q.options().dtype(at::kFloat));
+  auto o = at::empty({B, hq * d}, q.options());
+  FT_DISPATCH_E(q.scalar_type(), {
+    if (d == 64)
+      launch_attn_rows<E, 64>(q, k_cache, v_cache, part, o, pos0, (int)t, (int)max_keys, max_chunks, (int)B, (int)hq,
+                              (int)hkv);
+    else
+      launch_attn_rows<E, 128>(q, k_cache, v_cache, part, o, pos0, (int)t, (int)max_keys, max_chunks, (int)B, (int)hq,
+                               (int)hkv);
+  });
+  FT_LAUNCH_CHECK();
+  return o;
+}
 
 // y[N] = w[N, K] x[K] (+ residual[N]), fp32 accumulation, one rounding per output.
 at::Tensor gemv(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
@@ -692,5 +1041,12 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
         &decode_qkv_append_);
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, int n_keys) -> Tensor", &decode_attn);
   m.def("decode_attn_chunk() -> int", &decode_attn_chunk);
+  m.def("gemv_rows(Tensor x, Tensor w, Tensor? residual) -> Tensor", &gemv_rows);
+  m.def("gemv_swiglu_rows(Tensor x, Tensor w13) -> Tensor", &gemv_swiglu_rows);
+  m.def("decode_qkv_append_rows_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos0, int t, int max_pos, "
+        "Tensor(b!) k_cache, Tensor(c!) v_cache) -> ()",
+        &decode_qkv_append_rows_);
+  m.def("decode_attn_rows(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos0, int t, int max_keys) -> Tensor",
+        &decode_attn_rows);
   m.def("sample_(Tensor logits, Tensor(a!) out, float temperature, int top_k, int key, int step) -> ()", &sample_);
 }

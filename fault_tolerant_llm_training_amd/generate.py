@@ -5,6 +5,13 @@ the AdamW moments are never read) into a model of the given preset (``ckpt.state
 strict), generates with ``generation.generate`` and prints the decoded text; ``--json`` prints one
 line with the prompt ids, the generated ids, the text, the seconds and the tokens per second.
 A file that does not fit the model is reported as one error line and a non-zero exit code.
+
+Several sequences at once: ``--num-samples N`` draws N samples of the prompt, ``--prompts-file`` reads
+one prompt per line (``--prompt-ids-file``: comma-separated ids per line); with both, every prompt is
+repeated N times. More than one row goes through ``generation.generate_batch`` (one pass over the
+weights per token for all rows): ``--json`` then prints one line per row with a ``row`` field, the
+text mode a line ``--- sample b ---`` before each row. One row without these flags prints what it
+always printed.
 """
 from __future__ import annotations
 
@@ -31,6 +38,12 @@ def build_parser() -> argparse.ArgumentParser:
     g = p.add_mutually_exclusive_group()
     g.add_argument("--prompt", type=str, default=None, help="Prompt text (needs the tokenizer)")
     g.add_argument("--prompt-ids", type=str, default=None, help="Prompt as comma-separated token ids, e.g. 1,2,3")
+    g.add_argument("--prompts-file", type=str, default=None,
+                   help="File with one prompt per line (text, or comma-separated ids with --prompt-ids-file)")
+    p.add_argument("--prompt-ids-file", action="store_true", help="The lines of --prompts-file are token ids")
+    p.add_argument("--num-samples", type=int, default=1,
+                   help="Samples per prompt, generated as one batch (at most 64 rows in all); use a --temperature "
+                   "above 0, greedy samples of one prompt are identical")
     p.add_argument("--max-new-tokens", type=int, default=64)
     p.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
     p.add_argument("--top-k", type=int, default=0, help="0: all tokens")
@@ -48,7 +61,7 @@ def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     from .ckpt.format import load_checkpoint
     from .ckpt.state import restore_model
-    from .generation import generate
+    from .generation import MAX_BATCH, generate, generate_batch
     from .models.llama import PRESETS, build_model, model_args_for
     from .utils.config import PRECISION_STR_TO_DTYPE
     from .utils.sround import key_from_seed
@@ -59,8 +72,22 @@ def main(argv=None) -> int:
         return _fail(f"unknown --model-dtype {args.model_dtype!r}")
     if args.max_new_tokens < 1 or args.temperature < 0 or args.top_k < 0:
         return _fail("--max-new-tokens must be >= 1, --temperature and --top-k >= 0")
+    if args.num_samples < 1:
+        return _fail("--num-samples must be >= 1")
+    if args.prompt_ids_file and args.prompts_file is None:
+        return _fail("--prompt-ids-file needs --prompts-file")
+    lines = None
+    if args.prompts_file is not None:
+        try:
+            with open(args.prompts_file) as f:
+                lines = [ln.rstrip("\n") for ln in f if ln.strip()]
+        except OSError as e:
+            return _fail(f"cannot read {args.prompts_file}: {e!r}")
+        if not lines:
+            return _fail(f"{args.prompts_file} holds no prompt")
+    ids_given = args.prompt_ids is not None or (lines is not None and args.prompt_ids_file)
     tok = None
-    if args.prompt_ids is None or not args.vocab_size:
+    if not ids_given or not args.vocab_size:
         from .data.tokenizer import load_tokenizer
 
         try:
@@ -69,7 +96,15 @@ def main(argv=None) -> int:
             return _fail(f"cannot load the tokenizer {args.tokenizer_name_or_path!r} ({e!r}); "
                          "give --prompt-ids and --vocab-size to do without one")
     try:
-        if args.prompt_ids is not None:
+        if lines is not None and args.prompt_ids_file:
+            prompts = [[int(s) for s in ln.split(",") if s.strip()] for ln in lines]
+        elif lines is not None:
+            from .data.tokenizer import encode
+
+            prompts = [encode(tok, ln) for ln in lines]
+        if lines is not None:
+            prompt = prompts[0]
+        elif args.prompt_ids is not None:
             prompt = [int(s) for s in args.prompt_ids.split(",") if s.strip()]
         elif args.prompt is not None:
             from .data.tokenizer import encode
@@ -80,8 +115,14 @@ def main(argv=None) -> int:
             prompt = [1 if bos is None else int(bos)]
     except ValueError as e:
         return _fail(f"--prompt-ids: {e}")
-    if not prompt:
+    if lines is None:
+        prompts = [prompt]
+    if not all(prompts):
         return _fail("the prompt is empty")
+    prompts = [p for p in prompts for _ in range(args.num_samples)]
+    if len(prompts) > MAX_BATCH:
+        return _fail(f"{len(prompts)} rows (prompts x --num-samples) exceed the batch limit of {MAX_BATCH}")
+    batched = lines is not None or args.num_samples > 1
     vocab = args.vocab_size or int(tok.vocab_size)
     try:
         ckpt = load_checkpoint(args.checkpoint)
@@ -111,11 +152,26 @@ def main(argv=None) -> int:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     try:
-        ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                       key=key_from_seed(args.seed), eos_id=eos)
+        if batched:
+            rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
+                                  key=key_from_seed(args.seed), eos_id=eos)
+        else:
+            ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
+                           key=key_from_seed(args.seed), eos_id=eos)
     except ValueError as e:
         return _fail(str(e))
     dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished
+    if batched:
+        total = sum(len(r) for r in rows)
+        for b, (p, r) in enumerate(zip(prompts, rows)):
+            text = tok.decode(r) if tok is not None else ""
+            if args.json:  # seconds: the whole batch; tokens_per_s: all rows' tokens over it
+                print(json.dumps({"row": b, "prompt_ids": p, "ids": r, "text": text, "seconds": dt,
+                                  "tokens_per_s": total / dt if dt > 0 else 0.0}), flush=True)
+            else:
+                print(f"--- sample {b} ---", flush=True)
+                print(text if tok is not None else ",".join(str(i) for i in r), flush=True)
+        return 0
     text = tok.decode(ids) if tok is not None else ""
     if args.json:
         print(json.dumps({"prompt_ids": prompt, "ids": ids, "text": text, "seconds": dt,

@@ -10,6 +10,13 @@ token's position, K and V into the cache), ``decode_attn`` over the cache, ``gem
 (``ops/decode.py``): a cache of rotated K and V with the math of ``attention_reference``. That path
 is the definition; tests compare it with ``Transformer.forward``.
 
+Several sequences at once (:func:`generate_batch`): every prompt is prefilled on its own into its row
+of a :class:`BatchKVCache`, then one :func:`decode_step_rows` per token serves all B rows with the
+multi-row kernels (``gemv_rows``, ``gemv_swiglu_rows``, ``decode_qkv_append_rows_``,
+``decode_attn_rows``), which read every weight once for up to 8 rows. Each of those returns for a row
+the bits the one-row op returns for it alone, so a row's tokens do not depend on its batch: under
+greedy decoding ``generate_batch(model, prompts, ...)[b] == generate(model, prompts[b], ...)``.
+
 Generation always uses plain causal attention: a model with a document mask set generates one
 continuing document. Everything runs under ``torch.no_grad()`` and writes nothing of the training
 state (no gradient buffer, no sink, no optimizer state).
@@ -50,6 +57,73 @@ class KVCache:
         self.v = torch.zeros(shape, dtype=dtype, device=device)
         self.max_len = max_len
         self.length = 0
+
+
+class _CacheRow:
+    """Row ``b`` of a :class:`BatchKVCache` behind :class:`KVCache`'s interface: ``k`` / ``v`` are the
+    views ``[layers, Hkv, max_len, D]`` of that row (``k[i]`` is contiguous), ``length`` is the row's
+    entry of the batch's ``lengths``."""
+
+    def __init__(self, cache: "BatchKVCache", b: int):
+        self._cache, self._b = cache, b
+        self.k, self.v = cache.k[:, b], cache.v[:, b]
+        self.max_len = cache.max_len
+
+    @property
+    def length(self) -> int:
+        return self._cache.lengths[self._b]
+
+    @length.setter
+    def length(self, n: int) -> None:
+        self._cache.set_length(self._b, n)
+
+
+class BatchKVCache:
+    """The caches of ``batch`` sequences: ``k`` / ``v`` ``[layers, B, Hkv, max_len, D]``, so ``k[i]`` is
+    the contiguous per-layer operand of the multi-row kernels and ``k[i, b]`` that of the one-row ones.
+    ``lengths`` (host) and ``pos0`` (the same numbers, int32 on the device) hold every row's token
+    count when batched decoding starts; decode step ``t`` then works at position ``pos0[b] + t`` of
+    row ``b``, and ``steps`` counts the steps taken. ``row(b)`` is the row as a :class:`KVCache`, which
+    :func:`prefill` fills."""
+
+    def __init__(self, model_args, batch: int, max_len: int, device, dtype):
+        batch, max_len = int(batch), int(max_len)
+        if batch < 1:
+            raise ValueError(f"BatchKVCache: batch {batch} must be >= 1")
+        if max_len < 1 or max_len > model_args.seq_len:
+            raise ValueError(f"BatchKVCache: max_len {max_len} outside [1, {model_args.seq_len}] "
+                             "(the model's sequence length, which sizes its RoPE tables)")
+        shape = (model_args.n_layers, batch, model_args.kv_heads, max_len, model_args.head_dim)
+        self.k = torch.zeros(shape, dtype=dtype, device=device)
+        self.v = torch.zeros(shape, dtype=dtype, device=device)
+        self.batch, self.max_len = batch, max_len
+        self.lengths = [0] * batch
+        self.steps = 0
+        self._pos0: Optional[torch.Tensor] = None
+
+    def row(self, b: int) -> _CacheRow:
+        if not 0 <= b < self.batch:
+            raise IndexError(f"row {b} outside the batch of {self.batch}")
+        return _CacheRow(self, b)
+
+    def set_length(self, b: int, n: int) -> None:
+        if self.steps:
+            raise ValueError("a row's length is fixed once batched decoding has started")
+        self.lengths[b] = int(n)
+        self._pos0 = None
+
+    def copy_row(self, dst: int, src: int) -> None:
+        """Row ``dst`` becomes a copy of row ``src`` (an identical prompt is prefilled once)."""
+        n = self.lengths[src]
+        self.k[:, dst, :, :n] = self.k[:, src, :, :n]
+        self.v[:, dst, :, :n] = self.v[:, src, :, :n]
+        self.set_length(dst, n)
+
+    @property
+    def pos0(self) -> torch.Tensor:
+        if self._pos0 is None:
+            self._pos0 = torch.tensor(self.lengths, dtype=torch.int32, device=self.k.device)
+        return self._pos0
 
 
 def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor]) -> torch.Tensor:
@@ -133,6 +207,108 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache) -> torch
         d = D.gemv(D.gemv_swiglu(hn.reshape(-1), ff.w13), ff.w2.weight).view(1, -1)
     cache.length = pos + 1
     return _final_logits(model, h, d)
+
+
+@torch.no_grad()
+def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: BatchKVCache, t: int) -> torch.Tensor:
+    """Decode step ``t`` (0, 1, ...) of a batch: append ``tokens[b]`` at position ``pos0[b] + t`` of
+    row ``b``; returns the logits [B, V] after them. The loop of :func:`decode_step` on B rows."""
+    B, t = cache.batch, int(t)
+    if t != cache.steps:
+        raise ValueError(f"decode step {t} out of order (the cache has taken {cache.steps})")
+    if min(cache.lengths) < 1:
+        raise ValueError("every row needs a prefilled prompt")
+    if max(cache.lengths) + t >= cache.max_len:
+        raise ValueError(f"the cache is full ({cache.max_len} tokens)")
+    dev = cache.k.device
+    tok = torch.as_tensor(tokens, dtype=torch.int64).reshape(B, 1).to(dev)
+    a = model.model_args
+    ln = a.norm_type == "layernorm"
+    hq, hd = a.n_heads, a.head_dim
+    emb_r, layer_r, _ = model._ranges
+    model._wait(emb_r)
+    h = Fx.embedding(tok, model.tok_embeddings.weight, None).view(B, -1)
+    cos, sin = model.rope_cos, model.rope_sin
+    pos0, lengths = cache.pos0, cache.lengths
+    d = None
+    for i, layer in enumerate(model.layers.values()):
+        model._wait(layer_r[i])
+        at, ff = layer.attention, layer.feed_forward
+        if d is None:
+            xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
+        else:
+            h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
+        qkv = D.gemv_rows(xn, at.wqkv)
+        D.qkv_append_rows_(qkv, cos, sin, pos0, t, cache.k[i], cache.v[i], lengths)
+        o = D.attn_rows(qkv[:, : hq * hd], cache.k[i], cache.v[i], pos0, t, lengths)
+        da = D.gemv_rows(o, at.wo.weight)
+        h, hn = Fx.add_norm(h, da, layer.ffn_norm.weight, None, a.norm_eps, ln)
+        d = D.gemv_rows(D.gemv_swiglu_rows(hn, ff.w13), ff.w2.weight)
+    cache.steps = t + 1
+    model._wait(model._ranges[2])
+    if d is None:
+        hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
+    else:
+        _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
+    return D.gemv_rows(hn, model.output.weight)
+
+
+def _check_request(a, prompt: List[int], n_new: int, who: str) -> None:
+    if not prompt:
+        raise ValueError(f"{who} needs a prompt of at least one token")
+    if n_new < 0 or len(prompt) + n_new > a.seq_len:
+        raise ValueError(f"prompt ({len(prompt)}) + new tokens ({n_new}) exceed the model's sequence length "
+                         f"{a.seq_len}")
+    bad = [t for t in prompt if not 0 <= t < a.vocab_size]
+    if bad:
+        raise ValueError(f"prompt id {bad[0]} outside the vocabulary [0, {a.vocab_size})")
+
+
+MAX_BATCH = 64
+
+
+@torch.no_grad()
+def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0,
+                   top_k: int = 0, key: int = 0, eos_id: Optional[int] = None, step: int = 0) -> List[List[int]]:
+    """:func:`generate` for B prompts at once: the ids generated after each of ``prompts``. New token
+    ``t`` of every row comes from one ``D.sample(logits[B, V], ..., token_key(key, t), step)``, row
+    ``b``'s draw being the sampler's row ``b``: row 0 equals ``generate`` with the same arguments, and
+    copies of one prompt give different samples. A row that has emitted ``eos_id`` ends there (the id
+    included) and keeps its batch slot -- its further tokens are computed and dropped, so no other
+    row's draw or position shifts. Identical prompts are prefilled once."""
+    rows = [[int(t) for t in p] for p in prompts]
+    n_new = int(max_new_tokens)
+    a = model.model_args
+    B = len(rows)
+    if not 1 <= B <= MAX_BATCH:
+        raise ValueError(f"generate_batch takes 1 .. {MAX_BATCH} prompts, got {B}")
+    for p in rows:
+        _check_request(a, p, n_new, "generate_batch")
+    if n_new == 0:
+        return [[] for _ in rows]
+    flat = model.flat
+    cache = BatchKVCache(a, B, max(len(p) for p in rows) + n_new, flat.device, flat.dtype)
+    first, first_logits = {}, []
+    for b, p in enumerate(rows):
+        src = first.setdefault(tuple(p), b)
+        if src == b:
+            first_logits.append(prefill(model, p, cache.row(b)))
+        else:
+            cache.copy_row(b, src)
+            first_logits.append(first_logits[src])
+    logits = torch.stack(first_logits)
+    out: List[List[int]] = [[] for _ in rows]
+    live = [True] * B
+    for t in range(n_new):
+        nxt = D.sample(logits, temperature, top_k, token_key(key, t), step)
+        for b, tok in enumerate(nxt.tolist()):
+            if live[b]:
+                out[b].append(tok)
+                live[b] = eos_id is None or tok != eos_id
+        if not any(live) or t == n_new - 1:
+            break
+        logits = decode_step_rows(model, nxt, cache, t)
+    return out
 
 
 @torch.no_grad()

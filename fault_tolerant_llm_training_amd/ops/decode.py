@@ -1,4 +1,5 @@
-"""One-row (decode) ops of text generation: wrappers of csrc/kernels/decode.hip.
+"""One-row (decode) ops of text generation and their multi-row forms: wrappers of
+csrc/kernels/decode.hip.
 
 GPU tensors of a kernel dtype run the HIP kernels (``kernels()`` raises if the library is
 missing); CPU tensors and fp64 take the composed-PyTorch definition of the same math, as in
@@ -7,7 +8,7 @@ missing); CPU tensors and fp64 take the composed-PyTorch definition of the same 
 from __future__ import annotations
 
 import math
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -68,6 +69,50 @@ def attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_keys: 
     v = v_cache[:, :n_keys].repeat_interleave(hq // hkv, dim=0)
     s = torch.einsum("hd,hnd->hn", q.view(hq, d), k) / math.sqrt(d)
     return torch.einsum("hn,hnd->hd", F.softmax(s, dim=-1), v).reshape(-1)
+
+
+# ---------------------------------------------------------------------------------------------
+# The multi-row forms (batched generation). Row r of each result has the bits the one-row op above
+# returns for that row alone, on either route: the kernels keep the per-row arithmetic order, and
+# the composed definition is a loop over rows of the one-row definitions.
+# ---------------------------------------------------------------------------------------------
+def _gemv_rows_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
+    """``_gemv_ok`` for x [R, K], R >= 1."""
+    return x.dim() == 2 and x.shape[0] >= 1 and x.is_contiguous() and _gemv_ok(x[0], w)
+
+
+def gemv_rows(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[R, N] = x[R, K] w[N, K]^T (+ residual[R, N]); row r equals ``gemv(x[r], w, residual[r])``."""
+    if _gemv_rows_ok(x, w):
+        return kernels().gemv_rows(x, w, None if residual is None else residual.contiguous())
+    return torch.stack([gemv(x[r], w, None if residual is None else residual[r]) for r in range(x.shape[0])])
+
+
+def gemv_swiglu_rows(x: torch.Tensor, w13: torch.Tensor) -> torch.Tensor:
+    """a[R, H]; row r equals ``gemv_swiglu(x[r], w13)``."""
+    if _gemv_rows_ok(x, w13) and w13.shape[0] % 2 == 0:
+        return kernels().gemv_swiglu_rows(x, w13)
+    return torch.stack([gemv_swiglu(x[r], w13) for r in range(x.shape[0])])
+
+
+def qkv_append_rows_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, t: int,
+                     k_cache: torch.Tensor, v_cache: torch.Tensor, positions: Sequence[int]) -> None:
+    """``qkv_append_`` on row b of qkv [B, (Hq + 2 Hkv) D] at position ``pos0[b] + t`` of the caches
+    [B, Hkv, Smax, D]. ``positions`` is the host's copy of ``pos0``: the kernel route takes only its
+    maximum from it (the bound the op checks), so the device tensor is never read back."""
+    if native(qkv):
+        kernels().decode_qkv_append_rows_(qkv, cos, sin, pos0, int(t), max(positions) + int(t), k_cache, v_cache)
+        return
+    for b, p in enumerate(positions):
+        qkv_append_(qkv[b], cos, sin, int(p) + int(t), k_cache[b], v_cache[b])
+
+
+def attn_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos0: torch.Tensor, t: int,
+              positions: Sequence[int]) -> torch.Tensor:
+    """o[B, Hq D]; row b equals ``attn(q[b], k_cache[b], v_cache[b], pos0[b] + t + 1)``."""
+    if native(q):
+        return kernels().decode_attn_rows(q, k_cache, v_cache, pos0, int(t), max(positions) + int(t) + 1)
+    return torch.stack([attn(q[b], k_cache[b], v_cache[b], int(p) + int(t) + 1) for b, p in enumerate(positions)])
 
 
 def sample(logits: torch.Tensor, temperature: float, top_k: int, key: int, step: int) -> torch.Tensor:

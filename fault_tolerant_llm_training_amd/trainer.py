@@ -672,6 +672,7 @@ def train(args) -> int:
                 metrics_f.flush()
 
     sample_every = int(getattr(args, "sample_every", 0) or 0)
+    sample_count = int(getattr(args, "sample_count", 1) or 1)
     sample_prompt, sample_tok = None, None
     if sample_every > 0:
         from . import generation
@@ -688,6 +689,8 @@ def train(args) -> int:
             raise ValueError(f"--sample-every: prompt ({len(sample_prompt)} tokens) + --sample-tokens "
                              f"({args.sample_tokens}) exceed --sequence-length ({S})")
         sample_key = key_from_seed(args.seed)
+        if sample_count > 1:
+            logger.info(f"Sampling: {sample_count} samples per boundary, decoded as one batch")
         logger.info(f"Sampling: every {sample_every} steps and after the last step -- rank 0 generates "
                     f"{args.sample_tokens} tokens from a prompt of {len(sample_prompt)} (temperature "
                     f"{args.sample_temperature:g}, top-k {args.sample_top_k}; key {sample_key:#018x} from --seed, "
@@ -704,15 +707,31 @@ def train(args) -> int:
         nonlocal pending_err
         t0 = time.perf_counter()
         try:
-            ids = generation.generate(model, sample_prompt, args.sample_tokens, temperature=args.sample_temperature,
-                                      top_k=args.sample_top_k, key=sample_key, step=step_now,
-                                      eos_id=getattr(sample_tok, "eos_token_id", None))
+            if sample_count > 1:  # --sample-count: N copies of the prompt, one batch
+                rows = generation.generate_batch(model, [sample_prompt] * sample_count, args.sample_tokens,
+                                                 temperature=args.sample_temperature, top_k=args.sample_top_k,
+                                                 key=sample_key, step=step_now,
+                                                 eos_id=getattr(sample_tok, "eos_token_id", None))
+            else:
+                ids = generation.generate(model, sample_prompt, args.sample_tokens,
+                                          temperature=args.sample_temperature, top_k=args.sample_top_k,
+                                          key=sample_key, step=step_now,
+                                          eos_id=getattr(sample_tok, "eos_token_id", None))
         except Exception as e:  # noqa: BLE001 - becomes this rank's vote: every rank stops at the next boundary
             logger.error(f"Sample error at step {step_now}: {e!r}")
             if pending_err is None:
                 pending_err = e
             return
         dt = time.perf_counter() - t0
+        if sample_count > 1:
+            texts = [sample_tok.decode(r) if sample_tok is not None else " ".join(str(i) for i in r) for r in rows]
+            for b, (r, text) in enumerate(zip(rows, texts)):
+                logger.info(f"Sample {b} at step {step_now} | {text!r} | {len(r)} tokens | {dt:.2f} s")
+            if metrics_f is not None:
+                metrics_f.write(json.dumps({"sample_step": step_now, "sample_ids": rows, "sample_text": texts,
+                                            "sample_s": dt}) + "\n")
+                metrics_f.flush()
+            return
         text = sample_tok.decode(ids) if sample_tok is not None else " ".join(str(i) for i in ids)
         logger.info(f"Sample at step {step_now} | {text!r} | {len(ids)} tokens | {dt:.2f} s")
         if metrics_f is not None:

@@ -335,6 +335,15 @@ def build_parser() -> argparse.ArgumentParser:
     )
     parser.add_argument("--sample-top-k", type=int, default=0, help="Top-k of --sample-every (0: all tokens)")
     parser.add_argument(
+        "--sample-count",
+        type=int,
+        default=1,
+        help="Samples per --sample-every boundary (1 .. 16). Above 1, rank 0 decodes N copies of --sample-prompt "
+        "in one batch with the multi-row decode kernels (one pass over the weights per token for all of them): "
+        "sample 0 is the sample of --sample-count 1, the others are further draws, so use a --sample-temperature "
+        "above 0 (greedy copies are identical)",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -369,6 +378,10 @@ def get_args(argv=None) -> argparse.Namespace:
         parser.error(f"--tensor-stats-every must be >= 0, got {args.tensor_stats_every}")
     if args.sample_every < 0:
         parser.error(f"--sample-every must be >= 0, got {args.sample_every}")
+    if not 1 <= args.sample_count <= 16:
+        parser.error(f"--sample-count must be in 1 .. 16, got {args.sample_count}")
+    if args.sample_count > 1 and args.sample_every == 0:
+        parser.error("--sample-count needs --sample-every")
     if args.sample_every > 0:
         if not 1 <= args.sample_tokens <= 1024:
             parser.error(f"--sample-tokens must be in 1 .. 1024, got {args.sample_tokens}")
