@@ -25,6 +25,13 @@
 //
 // Positions, key counts and the sampler's step are host integers (kernel arguments); the `_rows` ops
 // take each row's start position from a device tensor `pos0` plus one host integer `t`.
+//
+// The device-step forms (decode_qkv_append_rows_dev_, decode_attn_rows_dev, sample_dev_) are the
+// `_rows` ops and the sampler with every per-token value read from a control block `ctl` in device
+// memory (CTL_* below) and with grids that do not depend on it, so one captured launch of each is
+// right for any token of any call (generation.DecodeGraph). They run the same per-row code and
+// return the same bits. decode_ctl_advance_ steps the counter in a launch of its own, after every
+// reader of the pass.
 #include <climits>
 
 #include "sround.h"
@@ -36,6 +43,18 @@ constexpr float LOG2E = 1.4426950408889634f;
 // keys per workgroup of decode_attn; the chunk partials are merged in chunk order
 constexpr int DECODE_CHUNK = 128;
 constexpr int SAMPLE_MAX_BLOCKS = 32768;
+
+// The control block of the device-step ops: int32 words (ops/decode.py keeps the same indices). The
+// host writes it once per call; the kernels only read it, but for decode_ctl_advance_ on CTL_T.
+enum : int {
+  CTL_T = 0,            // the decode step: new token t of the call
+  CTL_KEY_LO = 1,       // the call's sampler key (token_key is formed from it and t)
+  CTL_KEY_HI = 2,
+  CTL_STEP = 3,         // the sampler's step
+  CTL_TEMPERATURE = 4,  // float bits
+  CTL_TOP_K = 5,
+  CTL_WORDS = 8
+};
 
 // ---- one 16-byte vector of the model dtype: 8 elements (bf16 / fp16) or 4 (fp32)
 template <class E>
@@ -258,13 +277,10 @@ __global__ __launch_bounds__(256) void qkv_append_kernel(typename E::T* __restri
 // rotated and stored at pos0[b] + t. A position outside [0, limit) -- the host checked the largest one
 // the caller named, not pos0 itself -- writes nothing.
 template <class E>
-__global__ __launch_bounds__(256) void qkv_append_rows_kernel(typename E::T* __restrict__ qkv,
-                                                              const float* __restrict__ cos_t,
-                                                              const float* __restrict__ sin_t,
-                                                              const int* __restrict__ pos0, int t,
-                                                              typename E::T* __restrict__ kc,
-                                                              typename E::T* __restrict__ vc, int hq, int hkv,
-                                                              int d, long smax, long limit) {
+__device__ __forceinline__ void qkv_append_row(typename E::T* __restrict__ qkv, const float* __restrict__ cos_t,
+                                               const float* __restrict__ sin_t, const int* __restrict__ pos0, int t,
+                                               typename E::T* __restrict__ kc, typename E::T* __restrict__ vc, int hq,
+                                               int hkv, int d, long smax, long limit) {
   const int nvec = (hq + 2 * hkv) * d / 8;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
@@ -273,6 +289,31 @@ __global__ __launch_bounds__(256) void qkv_append_rows_kernel(typename E::T* __r
   const long cstride = (long)hkv * smax * d;
   qkv_append_vec<E>(i, qkv + (long)b * nvec * 8, cos_t + pos * (d / 2), sin_t + pos * (d / 2), kc + b * cstride,
                     vc + b * cstride, hq, hkv, d, smax, pos);
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void qkv_append_rows_kernel(typename E::T* __restrict__ qkv,
+                                                              const float* __restrict__ cos_t,
+                                                              const float* __restrict__ sin_t,
+                                                              const int* __restrict__ pos0, int t,
+                                                              typename E::T* __restrict__ kc,
+                                                              typename E::T* __restrict__ vc, int hq, int hkv,
+                                                              int d, long smax, long limit) {
+  qkv_append_row<E>(qkv, cos_t, sin_t, pos0, t, kc, vc, hq, hkv, d, smax, limit);
+}
+
+// decode_qkv_append_rows_dev_: t from the control block; limit is the capacity (the cache and the
+// RoPE tables), the only bound the host can name without knowing t.
+template <class E>
+__global__ __launch_bounds__(256) void qkv_append_rows_dev_kernel(typename E::T* __restrict__ qkv,
+                                                                  const float* __restrict__ cos_t,
+                                                                  const float* __restrict__ sin_t,
+                                                                  const int* __restrict__ pos0,
+                                                                  const int* __restrict__ ctl,
+                                                                  typename E::T* __restrict__ kc,
+                                                                  typename E::T* __restrict__ vc, int hq, int hkv,
+                                                                  int d, long smax, long limit) {
+  qkv_append_row<E>(qkv, cos_t, sin_t, pos0, ctl[CTL_T], kc, vc, hq, hkv, d, smax, limit);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -407,6 +448,20 @@ __device__ __forceinline__ int row_keys(const int* __restrict__ pos0, int b, int
 // starts at or beyond its row's key count leaves here, all of it, before the first barrier: its
 // slice of `part` stays unwritten and the merge below never reads it.
 template <class E, int D, int GT>
+__device__ __forceinline__ void attn_rows_chunk(const typename E::T* __restrict__ q,
+                                                const typename E::T* __restrict__ kc,
+                                                const typename E::T* __restrict__ vc, float* __restrict__ part,
+                                                const int* __restrict__ pos0, int t, int max_keys, long q_stride,
+                                                int hq, int hkv, long smax, float scale) {
+  const int b = blockIdx.z;
+  const int n_keys = row_keys(pos0, b, t, max_keys);
+  if ((int)blockIdx.y * DECODE_CHUNK >= n_keys) return;  // uniform over the workgroup
+  const long cstride = (long)hkv * smax * D;
+  attn_chunk<E, D, GT>(q + b * q_stride, kc + b * cstride, vc + b * cstride,
+                       part + (long)b * gridDim.y * hq * (D + 2), hq, hkv, smax, n_keys, scale);
+}
+
+template <class E, int D, int GT>
 __global__ __launch_bounds__(256) void decode_attn_rows_kernel(const typename E::T* __restrict__ q,
                                                                const typename E::T* __restrict__ kc,
                                                                const typename E::T* __restrict__ vc,
@@ -414,12 +469,20 @@ __global__ __launch_bounds__(256) void decode_attn_rows_kernel(const typename E:
                                                                const int* __restrict__ pos0, int t, int max_keys,
                                                                long q_stride, int hq, int hkv, long smax,
                                                                float scale) {
-  const int b = blockIdx.z;
-  const int n_keys = row_keys(pos0, b, t, max_keys);
-  if ((int)blockIdx.y * DECODE_CHUNK >= n_keys) return;  // uniform over the workgroup
-  const long cstride = (long)hkv * smax * D;
-  attn_chunk<E, D, GT>(q + b * q_stride, kc + b * cstride, vc + b * cstride,
-                       part + (long)b * gridDim.y * hq * (D + 2), hq, hkv, smax, n_keys, scale);
+  attn_rows_chunk<E, D, GT>(q, kc, vc, part, pos0, t, max_keys, q_stride, hq, hkv, smax, scale);
+}
+
+// decode_attn_rows_dev: t from the control block, the grid over the whole capacity (max_keys = Smax),
+// so most workgroups of a short row leave at the test above.
+template <class E, int D, int GT>
+__global__ __launch_bounds__(256) void decode_attn_rows_dev_kernel(const typename E::T* __restrict__ q,
+                                                                   const typename E::T* __restrict__ kc,
+                                                                   const typename E::T* __restrict__ vc,
+                                                                   float* __restrict__ part,
+                                                                   const int* __restrict__ pos0,
+                                                                   const int* __restrict__ ctl, long q_stride,
+                                                                   int hq, int hkv, long smax, float scale) {
+  attn_rows_chunk<E, D, GT>(q, kc, vc, part, pos0, ctl[CTL_T], (int)smax, q_stride, hq, hkv, smax, scale);
 }
 
 // One workgroup per query head, one thread per dim: the chunk partials in chunk order.
@@ -449,14 +512,30 @@ __global__ __launch_bounds__(D) void decode_attn_merge_kernel(const float* __res
 
 // Grid (Hq, B): row b folds its own ceil(keys / DECODE_CHUNK) chunks of part [B, max_chunks, Hq, D + 2].
 template <class E, int D>
-__global__ __launch_bounds__(D) void decode_attn_merge_rows_kernel(const float* __restrict__ part,
-                                                                   typename E::T* __restrict__ o,
-                                                                   const int* __restrict__ pos0, int t,
-                                                                   int max_keys, int max_chunks, int hq) {
+__device__ __forceinline__ void attn_merge_row(const float* __restrict__ part, typename E::T* __restrict__ o,
+                                               const int* __restrict__ pos0, int t, int max_keys, int max_chunks,
+                                               int hq) {
   const int b = blockIdx.y;
   const int n_keys = max(row_keys(pos0, b, t, max_keys), 0);
   attn_merge<E, D>(part + (long)b * max_chunks * hq * (D + 2), o + (long)b * hq * D, hq,
                    (n_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
+}
+
+template <class E, int D>
+__global__ __launch_bounds__(D) void decode_attn_merge_rows_kernel(const float* __restrict__ part,
+                                                                   typename E::T* __restrict__ o,
+                                                                   const int* __restrict__ pos0, int t,
+                                                                   int max_keys, int max_chunks, int hq) {
+  attn_merge_row<E, D>(part, o, pos0, t, max_keys, max_chunks, hq);
+}
+
+template <class E, int D>
+__global__ __launch_bounds__(D) void decode_attn_merge_rows_dev_kernel(const float* __restrict__ part,
+                                                                       typename E::T* __restrict__ o,
+                                                                       const int* __restrict__ pos0,
+                                                                       const int* __restrict__ ctl, int max_keys,
+                                                                       int max_chunks, int hq) {
+  attn_merge_row<E, D>(part, o, pos0, ctl[CTL_T], max_keys, max_chunks, hq);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -511,10 +590,13 @@ __device__ __forceinline__ int block_min(int v, int* sh) {
   return v;
 }
 
+// The passes, on rows blockIdx.x, blockIdx.x + gridDim.x, ...: row r's token goes to out[r] and, where
+// `col` is given, to col[r * col_stride] as well (sample_dev_: column t of the call's token table).
 template <class E>
-__global__ __launch_bounds__(256) void sample_kernel(const typename E::T* __restrict__ logits,
-                                                     int64_t* __restrict__ out, int V, int R, float temperature,
-                                                     int top_k, uint32_t key_lo, uint32_t key_hi, uint32_t step) {
+__device__ __forceinline__ void sample_rows(const typename E::T* __restrict__ logits, int64_t* __restrict__ out,
+                                            int64_t* __restrict__ col, long col_stride, int V, int R,
+                                            float temperature, int top_k, uint32_t key_lo, uint32_t key_hi,
+                                            uint32_t step) {
   __shared__ float sh_m[4];
   __shared__ int sh_i[4];
   __shared__ double sh_d[4];
@@ -562,7 +644,10 @@ __global__ __launch_bounds__(256) void sample_kernel(const typename E::T* __rest
     __syncthreads();
     if (mi == INT_MAX) mi = 0;  // a row without a single ordered value (all NaN)
     if (temperature == 0.f) {
-      if (tid == 0) out[row] = mi;
+      if (tid == 0) {
+        out[row] = mi;
+        if (col != nullptr) col[(long)row * col_stride] = mi;
+      }
       continue;
     }
     // ---- passes B: candidates are key > thr, or key == thr at a column <= tie_last
@@ -692,9 +777,42 @@ __global__ __launch_bounds__(256) void sample_kernel(const typename E::T* __rest
       last = -block_min(-last, sh_i);
       found = last >= 0 ? last : mi;
     }
-    if (tid == 0) out[row] = found;
+    if (tid == 0) {
+      out[row] = found;
+      if (col != nullptr) col[(long)row * col_stride] = found;
+    }
     __syncthreads();
   }
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void sample_kernel(const typename E::T* __restrict__ logits,
+                                                     int64_t* __restrict__ out, int V, int R, float temperature,
+                                                     int top_k, uint32_t key_lo, uint32_t key_hi, uint32_t step) {
+  sample_rows<E>(logits, out, nullptr, 0, V, R, temperature, top_k, key_lo, key_hi, step);
+}
+
+// sample_dev_: the sampling arguments from the control block, and the per-token key
+// token_key(key, t) = (key + (t + 1) * 0x9E3779B97F4A7C15) mod 2^63 formed here (generation.token_key).
+// Tokens go to tok[R] and to column t of out [R, n_cap]; a t outside [0, n_cap) writes tok alone.
+template <class E>
+__global__ __launch_bounds__(256) void sample_dev_kernel(const typename E::T* __restrict__ logits,
+                                                         const int* __restrict__ ctl, int64_t* __restrict__ tok,
+                                                         int64_t* __restrict__ out, long n_cap, int V, int R) {
+  const int t = ctl[CTL_T];
+  const uint64_t key = (uint64_t)(uint32_t)ctl[CTL_KEY_LO] | ((uint64_t)(uint32_t)ctl[CTL_KEY_HI] << 32);
+  const uint64_t tk = (key + ((uint64_t)(int64_t)t + 1ull) * 0x9E3779B97F4A7C15ull) & 0x7FFFFFFFFFFFFFFFull;
+  const float temperature = __int_as_float(ctl[CTL_TEMPERATURE]);
+  const int top_k = min(max(ctl[CTL_TOP_K], 0), V);
+  int64_t* col = (t >= 0 && t < n_cap) ? out + t : nullptr;
+  sample_rows<E>(logits, tok, col, n_cap, V, R, temperature, top_k, (uint32_t)tk, (uint32_t)(tk >> 32),
+                 (uint32_t)ctl[CTL_STEP]);
+}
+
+// decode_ctl_advance_: t <- t + 1, one thread, a plain load and store. A launch of its own behind
+// every kernel of the pass: each of their workgroups reads t, so none of them may write it.
+__global__ void ctl_advance_kernel(int* __restrict__ ctl) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) ctl[CTL_T] = ctl[CTL_T] + 1;
 }
 
 void check_vec(const char* op, const at::Tensor& t, const char* name) {
@@ -834,6 +952,29 @@ void launch_attn_rows(const at::Tensor& q, const at::Tensor& kc, const at::Tenso
                      mptr<typename E::T>(o), cptr<int>(pos0), t, max_keys, max_chunks, hq);
 }
 
+template <class E, int D>
+void launch_attn_rows_dev(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& part,
+                          const at::Tensor& o, const at::Tensor& pos0, const at::Tensor& ctl, int max_chunks, int B,
+                          int hq, int hkv) {
+  const int G = hq / hkv;
+  const dim3 grid(hkv, max_chunks, B);
+  const float scale = 1.f / sqrtf((float)D);
+  const long smax = kc.size(2);
+#define FT_ATTN(GT)                                                                                       \
+  hipLaunchKernelGGL((decode_attn_rows_dev_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),            \
+                     cptr<typename E::T>(q), cptr<typename E::T>(kc), cptr<typename E::T>(vc), mptr<float>(part), \
+                     cptr<int>(pos0), cptr<int>(ctl), (long)q.stride(0), hq, hkv, smax, scale)
+  if (G == 1) FT_ATTN(1);
+  else if (G == 2) FT_ATTN(2);
+  else if (G <= 4) FT_ATTN(4);
+  else FT_ATTN(8);
+#undef FT_ATTN
+  FT_LAUNCH_CHECK();
+  hipLaunchKernelGGL((decode_attn_merge_rows_dev_kernel<E, D>), dim3(hq, B), dim3(D), 0, ft_stream(),
+                     cptr<float>(part), mptr<typename E::T>(o), cptr<int>(pos0), cptr<int>(ctl), (int)smax, max_chunks,
+                     hq);
+}
+
 // The operands the two batched cache ops share: caches [B, Hkv, Smax, D] of x's dtype, pos0 int32 [B].
 void check_rows(const char* op, const at::Tensor& x, const at::Tensor& k_cache, const at::Tensor& v_cache,
                 const at::Tensor& pos0) {
@@ -856,7 +997,112 @@ void check_rows(const char* op, const at::Tensor& x, const at::Tensor& k_cache, 
   TORCH_CHECK(x.size(0) <= 65535 && k_cache.size(2) <= INT_MAX, op, ": B or Smax too large");
 }
 
+void check_ctl(const char* op, const at::Tensor& ctl, const at::Tensor& like) {
+  TORCH_CHECK(ctl.is_cuda() && ctl.device() == like.device() && ctl.scalar_type() == at::kInt && ctl.is_contiguous() &&
+                  ctl.dim() == 1 && ctl.size(0) >= CTL_WORDS,
+              op, ": ctl must be a contiguous int32 tensor of at least ", (int)CTL_WORDS, " words on the operands' device");
+}
+
 }  // namespace
+
+// decode_qkv_append_rows_ with t read from ctl[CTL_T] on the device: row b goes to position
+// pos0[b] + t. The host does not know t, so the only bound here is the capacity: a position outside
+// the cache or the RoPE tables writes nothing (the caller checks its own count of steps).
+void decode_qkv_append_rows_dev_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
+                                 const at::Tensor& pos0, const at::Tensor& ctl, const at::Tensor& k_cache,
+                                 const at::Tensor& v_cache) {
+  const char* op = "decode_qkv_append_rows_dev_";
+  check_rows(op, qkv, k_cache, v_cache, pos0);
+  check_ctl(op, ctl, qkv);
+  TORCH_CHECK(qkv.is_contiguous(), op, ": qkv must be contiguous");
+  const int64_t B = qkv.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
+  TORCH_CHECK(d > 0 && d % 8 == 0, op, ": head_dim must be a multiple of 8");
+  TORCH_CHECK(qkv.size(1) % d == 0 && qkv.size(1) / d > 2 * hkv, op, ": qkv width");
+  const int64_t hq = qkv.size(1) / d - 2 * hkv;
+  for (const at::Tensor* c : {&cos_t, &sin_t}) {
+    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() && c->scalar_type() == at::kFloat && c->is_contiguous() &&
+                    c->dim() == 2 && c->size(1) == d / 2 && c->size(0) == cos_t.size(0),
+                op, ": cos / sin must be fp32 [S, D / 2] on qkv's device");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": cos / sin alignment");
+  }
+  const at::DeviceGuard guard(qkv.device());
+  const int nvec = (int)(qkv.size(1) / 8);
+  FT_DISPATCH_E(qkv.scalar_type(),
+                hipLaunchKernelGGL(qkv_append_rows_dev_kernel<E>, dim3((nvec + 255) / 256, (unsigned)B), dim3(256), 0,
+                                   ft_stream(), mptr<typename E::T>(qkv), cptr<float>(cos_t), cptr<float>(sin_t),
+                                   cptr<int>(pos0), cptr<int>(ctl), mptr<typename E::T>(k_cache),
+                                   mptr<typename E::T>(v_cache), (int)hq, (int)hkv, (int)d, (long)smax,
+                                   (long)std::min<int64_t>(smax, cos_t.size(0))));
+  FT_LAUNCH_CHECK();
+}
+
+// decode_attn_rows with t read from ctl[CTL_T] on the device, into the caller's buffers: part fp32
+// [B, ceil(Smax / DECODE_CHUNK), hq, d + 2] and o [B, hq d]. The grid covers the capacity, a row's
+// merge folds the chunks its key count min(pos0[b] + t + 1, Smax) needs: the bits of decode_attn_rows.
+void decode_attn_rows_dev(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                          const at::Tensor& pos0, const at::Tensor& ctl, const at::Tensor& part, const at::Tensor& o) {
+  const char* op = "decode_attn_rows_dev";
+  check_rows(op, q, k_cache, v_cache, pos0);
+  check_ctl(op, ctl, q);
+  const int64_t B = q.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
+  TORCH_CHECK(d == 64 || d == 128, op, ": head_dim must be 64 or 128");
+  TORCH_CHECK(q.size(1) % d == 0, op, ": q width");
+  const int64_t hq = q.size(1) / d;
+  TORCH_CHECK(hq > 0 && hq % hkv == 0, op, ": Hq must be a multiple of Hkv");
+  TORCH_CHECK(smax >= 1, op, ": empty cache");
+  const int64_t max_chunks = (smax + DECODE_CHUNK - 1) / DECODE_CHUNK;
+  TORCH_CHECK(max_chunks <= 65535, op, ": too many key chunks");
+  TORCH_CHECK(part.is_cuda() && part.device() == q.device() && part.scalar_type() == at::kFloat &&
+                  part.is_contiguous() && part.numel() == B * max_chunks * hq * (d + 2),
+              op, ": part must be a contiguous fp32 [B, ceil(Smax / ", DECODE_CHUNK, "), Hq, D + 2] tensor");
+  TORCH_CHECK(o.is_cuda() && o.device() == q.device() && o.scalar_type() == q.scalar_type() && o.is_contiguous() &&
+                  o.dim() == 2 && o.size(0) == B && o.size(1) == hq * d,
+              op, ": o must be a contiguous [B, Hq D] tensor of q's dtype");
+  const at::DeviceGuard guard(q.device());
+  FT_DISPATCH_E(q.scalar_type(), {
+    if (d == 64)
+      launch_attn_rows_dev<E, 64>(q, k_cache, v_cache, part, o, pos0, ctl, (int)max_chunks, (int)B, (int)hq, (int)hkv);
+    else
+      launch_attn_rows_dev<E, 128>(q, k_cache, v_cache, part, o, pos0, ctl, (int)max_chunks, (int)B, (int)hq,
+                                   (int)hkv);
+  });
+  FT_LAUNCH_CHECK();
+}
+
+// sample_ with (temperature, top_k, key, step) and the token number t read from ctl on the device:
+// row r draws what sample_(logits, ., temperature, top_k, token_key(key, t), step) draws for it, into
+// tok[r] and out[r, t] (out int64 [R, n_cap]).
+void sample_dev_(const at::Tensor& logits, const at::Tensor& ctl, const at::Tensor& tok, const at::Tensor& out) {
+  const char* op = "sample_dev_";
+  FT_CHECK_CUDA(logits);
+  FT_CHECK_MODEL_DTYPE(logits);
+  FT_CHECK_CONTIG(logits);
+  check_ctl(op, ctl, logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.size(0) > 0 && logits.size(1) > 0, op, ": logits must be [R, V]");
+  const int64_t R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V % 8 == 0, op, ": vocab must be a multiple of 8");
+  TORCH_CHECK(V <= INT_MAX && R <= INT_MAX, op, ": R and V must fit 32 bits");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, op, ": logits must be 16-byte aligned");
+  for (const at::Tensor* x : {&tok, &out})
+    TORCH_CHECK(x->is_cuda() && x->device() == logits.device() && x->scalar_type() == at::kLong && x->is_contiguous(),
+                op, ": tok and out must be contiguous int64 tensors on logits' device");
+  TORCH_CHECK(tok.numel() == R, op, ": tok holds one token per row");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == R && out.size(1) >= 1, op, ": out must be [R, n_cap]");
+  const at::DeviceGuard guard(logits.device());
+  FT_DISPATCH_E(logits.scalar_type(),
+                hipLaunchKernelGGL(sample_dev_kernel<E>, dim3((unsigned)std::min<int64_t>(R, SAMPLE_MAX_BLOCKS)),
+                                   dim3(256), 0, ft_stream(), cptr<typename E::T>(logits), cptr<int>(ctl),
+                                   mptr<int64_t>(tok), mptr<int64_t>(out), (long)out.size(1), (int)V, (int)R));
+  FT_LAUNCH_CHECK();
+}
+
+// ctl[CTL_T] += 1 on the device, in stream order behind the pass that read it.
+void decode_ctl_advance_(const at::Tensor& ctl) {
+  check_ctl("decode_ctl_advance_", ctl, ctl);
+  const at::DeviceGuard guard(ctl.device());
+  hipLaunchKernelGGL(ctl_advance_kernel, dim3(1), dim3(64), 0, ft_stream(), mptr<int>(ctl));
+  FT_LAUNCH_CHECK();
+}
 
 // y[R, N] = x[R, K] w[N, K]^T (+ residual[R, N]); row r has the bits of gemv(x[r], w, residual[r]).
 at::Tensor gemv_rows(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
@@ -1049,4 +1295,12 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
   m.def("decode_attn_rows(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos0, int t, int max_keys) -> Tensor",
         &decode_attn_rows);
   m.def("sample_(Tensor logits, Tensor(a!) out, float temperature, int top_k, int key, int step) -> ()", &sample_);
+  m.def("decode_qkv_append_rows_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos0, Tensor ctl, "
+        "Tensor(b!) k_cache, Tensor(c!) v_cache) -> ()",
+        &decode_qkv_append_rows_dev_);
+  m.def("decode_attn_rows_dev(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos0, Tensor ctl, Tensor(a!) part, "
+        "Tensor(b!) o) -> ()",
+        &decode_attn_rows_dev);
+  m.def("sample_dev_(Tensor logits, Tensor ctl, Tensor(a!) tok, Tensor(b!) out) -> ()", &sample_dev_);
+  m.def("decode_ctl_advance_(Tensor(a!) ctl) -> ()", &decode_ctl_advance_);
 }

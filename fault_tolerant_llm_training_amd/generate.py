@@ -12,6 +12,9 @@ repeated N times. More than one row goes through ``generation.generate_batch`` (
 weights per token for all rows): ``--json`` then prints one line per row with a ``row`` field, the
 text mode a line ``--- sample b ---`` before each row. One row without these flags prints what it
 always printed.
+
+``--decode-graph`` decodes with ``generation.DecodeGraph``: one captured HIP graph per token, replayed,
+instead of about nine launches per layer issued from Python. The ids are the same.
 """
 from __future__ import annotations
 
@@ -48,6 +51,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
     p.add_argument("--top-k", type=int, default=0, help="0: all tokens")
     p.add_argument("--seed", type=int, default=1234, help="Seed of the sampler key")
+    p.add_argument("--decode-graph", action="store_true",
+                   help="Decode by replaying one captured HIP graph per token instead of launching every kernel "
+                   "from Python (the same ids; GPU models of a kernel dtype with a vocabulary that is a multiple of 8, elsewhere ignored)")
     p.add_argument("--json", action="store_true", help="Print one JSON line instead of the text")
     return p
 
@@ -154,10 +160,10 @@ def main(argv=None) -> int:
     try:
         if batched:
             rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                                  key=key_from_seed(args.seed), eos_id=eos)
+                                  key=key_from_seed(args.seed), eos_id=eos, graph=args.decode_graph)
         else:
             ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                           key=key_from_seed(args.seed), eos_id=eos)
+                           key=key_from_seed(args.seed), eos_id=eos, graph=args.decode_graph)
     except ValueError as e:
         return _fail(str(e))
     dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished

@@ -4,11 +4,17 @@ csrc/kernels/decode.hip.
 GPU tensors of a kernel dtype run the HIP kernels (``kernels()`` raises if the library is
 missing); CPU tensors and fp64 take the composed-PyTorch definition of the same math, as in
 ``ops.functional``. ``generation.py`` is the caller.
+
+The device-step forms at the end (``qkv_append_rows_dev_``, ``attn_rows_dev``, ``sample_dev_``,
+``ctl_advance_``) take the per-token state -- the step ``t`` and the sampling arguments -- from a
+small control block ``ctl`` in device memory instead of from host arguments, so a captured launch of
+them serves every token of every call (``generation.DecodeGraph``).
 """
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence
+import struct
+from typing import Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -126,3 +132,96 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int, key: int, step:
     from ..utils.sampling import sample_reference
 
     return sample_reference(x2, temperature, top_k, key, step).to(x2.device)
+
+
+# ---------------------------------------------------------------------------------------------
+# The device-step forms. ``ctl`` is an int32 tensor of CTL_WORDS words on the operands' device (the
+# indices of csrc/kernels/decode.hip); the host writes it once per call with ``write_ctl`` and the
+# kernel route never reads it back. The composed route (CPU, fp64) reads it on the host and calls the
+# definitions above.
+# ---------------------------------------------------------------------------------------------
+CTL_T, CTL_KEY_LO, CTL_KEY_HI, CTL_STEP, CTL_TEMPERATURE, CTL_TOP_K = range(6)
+CTL_WORDS = 8
+_M32 = 0xFFFFFFFF
+
+
+def new_ctl(device) -> torch.Tensor:
+    return torch.zeros(CTL_WORDS, dtype=torch.int32, device=device)
+
+
+def write_ctl(ctl: torch.Tensor, t: int, temperature: float, top_k: int, key: int, step: int) -> None:
+    """Fill the control block: step counter ``t``, and the sampling arguments of ``sample`` -- the
+    temperature as the float32 the kernel takes, the call's key (not a token's) as two words."""
+    if not (0.0 <= float(temperature) < math.inf) or int(top_k) < 0 or int(t) < 0:
+        raise ValueError("temperature must be finite and >= 0, top_k and t >= 0")
+    tbits = struct.unpack("<I", struct.pack("<f", float(temperature)))[0]
+    words = [int(t) & _M32, int(key) & _M32, (int(key) >> 32) & _M32, int(step) & _M32, tbits,
+             min(int(top_k), 0x7FFFFFFF), 0, 0]
+    ctl.copy_(torch.tensor(struct.unpack("<8i", struct.pack("<8I", *words)), dtype=torch.int32))
+
+
+def read_ctl(ctl: torch.Tensor) -> Tuple[int, float, int, int, int]:
+    """``(t, temperature, top_k, key, step)`` of a control block, on the host (the composed route)."""
+    w = [int(x) & _M32 for x in ctl.tolist()]
+    t = w[CTL_T] - (1 << 32) if w[CTL_T] >> 31 else w[CTL_T]
+    temperature = struct.unpack("<f", struct.pack("<I", w[CTL_TEMPERATURE]))[0]
+    return t, temperature, w[CTL_TOP_K], w[CTL_KEY_LO] | (w[CTL_KEY_HI] << 32), w[CTL_STEP]
+
+
+def ctl_advance_(ctl: torch.Tensor) -> None:
+    """``t += 1``: on the device in stream order, behind every op of the pass that read ``t``."""
+    if ctl.is_cuda:
+        kernels().decode_ctl_advance_(ctl)
+    else:
+        ctl[CTL_T] += 1
+
+
+def qkv_append_rows_dev_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor,
+                         ctl: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor) -> None:
+    """``qkv_append_rows_`` with ``t`` taken from ``ctl``: row b at position ``pos0[b] + t``. A position
+    outside the cache or the RoPE tables writes nothing (and leaves that row's Q unrotated)."""
+    if native(qkv):
+        kernels().decode_qkv_append_rows_dev_(qkv, cos, sin, pos0, ctl, k_cache, v_cache)
+        return
+    t = read_ctl(ctl)[0]
+    limit = min(k_cache.shape[2], cos.shape[0])
+    for b, p in enumerate(pos0.tolist()):
+        if 0 <= p + t < limit:
+            qkv_append_(qkv[b], cos, sin, p + t, k_cache[b], v_cache[b])
+
+
+def attn_rows_dev(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos0: torch.Tensor,
+                  ctl: torch.Tensor, part: torch.Tensor, o: torch.Tensor) -> torch.Tensor:
+    """``attn_rows`` with ``t`` taken from ``ctl``, into the caller's ``o`` [B, Hq D]; ``part`` is the
+    kernel's workspace, fp32 ``[B, ceil(Smax / chunk), Hq, D + 2]`` (``attn_part``). Returns ``o``."""
+    if native(q):
+        kernels().decode_attn_rows_dev(q, k_cache, v_cache, pos0, ctl, part, o)
+        return o
+    t = read_ctl(ctl)[0]
+    o.copy_(attn_rows(q, k_cache, v_cache, pos0, t, pos0.tolist()))
+    return o
+
+
+def attn_part(batch: int, hq: int, smax: int, d: int, device) -> torch.Tensor:
+    """The workspace of ``attn_rows_dev`` for caches of capacity ``smax`` (one element where the composed
+    route runs, which needs none)."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        return torch.empty(1, dtype=torch.float32, device=dev)
+    chunk = int(kernels().decode_attn_chunk())
+    return torch.empty(batch, (smax + chunk - 1) // chunk, hq, d + 2, dtype=torch.float32, device=dev)
+
+
+def sample_dev_(logits: torch.Tensor, ctl: torch.Tensor, tok: torch.Tensor, out: torch.Tensor) -> None:
+    """``sample(logits, temperature, top_k, token_key(key, t), step)`` with all five taken from ``ctl``:
+    row b's token goes to ``tok[b]`` (int64, B elements) and to ``out[b, t]`` (int64 ``[B, n_cap]``)."""
+    if native(logits) and logits.dim() == 2 and logits.shape[1] % 8 == 0:
+        kernels().sample_dev_(logits, ctl, tok, out)
+        return
+    from ..utils.sampling import token_key
+
+    t, temperature, top_k, key, step = read_ctl(ctl)
+    nxt = sample(logits, temperature, top_k, token_key(key, t), step).to(tok.device)
+    tok.copy_(nxt.view_as(tok))
+    if 0 <= t < out.shape[1]:
+        out[:, t] = nxt

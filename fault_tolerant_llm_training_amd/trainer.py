@@ -689,6 +689,13 @@ def train(args) -> int:
             raise ValueError(f"--sample-every: prompt ({len(sample_prompt)} tokens) + --sample-tokens "
                              f"({args.sample_tokens}) exceed --sequence-length ({S})")
         sample_key = key_from_seed(args.seed)
+        if getattr(args, "sample_graph", False):
+            if generation.graph_supported(model):
+                logger.info("Sampling: --sample-graph, one captured decode graph replayed per token (captured at "
+                            "the first sample)")
+            else:
+                logger.info("Sampling: --sample-graph needs a GPU model of a kernel dtype with a vocabulary that is "
+                            "a multiple of 8; the samples are decoded eagerly")
         if sample_count > 1:
             logger.info(f"Sampling: {sample_count} samples per boundary, decoded as one batch")
         logger.info(f"Sampling: every {sample_every} steps and after the last step -- rank 0 generates "
@@ -696,6 +703,27 @@ def train(args) -> int:
                     f"{args.sample_temperature:g}, top-k {args.sample_top_k}; key {sample_key:#018x} from --seed, "
                     "sampler step = training step); the other ranks wait in the next vote (keep it far below "
                     "--peer-timeout)")
+
+    sample_graph = None  # --sample-graph: the run's DecodeGraph, built at the first boundary
+
+    def sample_rows(step_now: int):
+        """The boundary's samples, one list of ids per --sample-count row."""
+        nonlocal sample_graph
+        kw = dict(temperature=args.sample_temperature, top_k=args.sample_top_k, key=sample_key, step=step_now,
+                  eos_id=getattr(sample_tok, "eos_token_id", None))
+        if getattr(args, "sample_graph", False) and generation.graph_supported(model):
+            first = sample_graph is None
+            if first:  # here, not at start-up: the flat buffers' addresses are final
+                sample_graph = generation.DecodeGraph(model, sample_count, len(sample_prompt) + args.sample_tokens)
+            rows = sample_graph.run([sample_prompt] * sample_count, args.sample_tokens, **kw)
+            if first:
+                logger.info(f"Sampling: decode graph captured at step {step_now} ({sample_graph.batch} rows, "
+                            f"capacity {sample_graph.max_len}); captures {sample_graph.captures}, replays "
+                            f"{sample_graph.replays}")
+            return rows
+        if sample_count > 1:  # --sample-count: N copies of the prompt, one batch
+            return generation.generate_batch(model, [sample_prompt] * sample_count, args.sample_tokens, **kw)
+        return [generation.generate(model, sample_prompt, args.sample_tokens, **kw)]
 
     def sample_at(step_now: int) -> None:
         """--sample-every: one generated sample at step boundary ``step_now``, after the vote, a periodic
@@ -707,16 +735,8 @@ def train(args) -> int:
         nonlocal pending_err
         t0 = time.perf_counter()
         try:
-            if sample_count > 1:  # --sample-count: N copies of the prompt, one batch
-                rows = generation.generate_batch(model, [sample_prompt] * sample_count, args.sample_tokens,
-                                                 temperature=args.sample_temperature, top_k=args.sample_top_k,
-                                                 key=sample_key, step=step_now,
-                                                 eos_id=getattr(sample_tok, "eos_token_id", None))
-            else:
-                ids = generation.generate(model, sample_prompt, args.sample_tokens,
-                                          temperature=args.sample_temperature, top_k=args.sample_top_k,
-                                          key=sample_key, step=step_now,
-                                          eos_id=getattr(sample_tok, "eos_token_id", None))
+            rows = sample_rows(step_now)
+            ids = rows[0]
         except Exception as e:  # noqa: BLE001 - becomes this rank's vote: every rank stops at the next boundary
             logger.error(f"Sample error at step {step_now}: {e!r}")
             if pending_err is None:

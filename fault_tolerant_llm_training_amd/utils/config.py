@@ -344,6 +344,16 @@ def build_parser() -> argparse.ArgumentParser:
         "above 0 (greedy copies are identical)",
     )
     parser.add_argument(
+        "--sample-graph",
+        action="store_true",
+        help="Decode the samples of --sample-every by replaying one captured HIP graph per token "
+        "(generation.DecodeGraph) instead of launching every kernel from Python: the trainer captures it once, at "
+        "the first sample, sized from --sample-count, the prompt and --sample-tokens, and reuses it at every "
+        "boundary. The sample lines and records are those of a run without the flag and the training state stays "
+        "bit-identical; independent of --hip-graph. Needs --device cuda, a bf16/fp16/fp32 model and a vocabulary that is a "
+        "multiple of 8 (elsewhere the samples are decoded eagerly)",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -382,6 +392,8 @@ def get_args(argv=None) -> argparse.Namespace:
         parser.error(f"--sample-count must be in 1 .. 16, got {args.sample_count}")
     if args.sample_count > 1 and args.sample_every == 0:
         parser.error("--sample-count needs --sample-every")
+    if args.sample_graph and args.sample_every == 0:
+        parser.error("--sample-graph needs --sample-every")
     if args.sample_every > 0:
         if not 1 <= args.sample_tokens <= 1024:
             parser.error(f"--sample-tokens must be in 1 .. 1024, got {args.sample_tokens}")

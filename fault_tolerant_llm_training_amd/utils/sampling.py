@@ -22,6 +22,13 @@ import torch
 from .sround import BUF_SAMPLE, philox_words
 
 _CHUNK_ELEMS = 1 << 24  # rows are processed in chunks of about this many float64 logits
+_MASK63 = (1 << 63) - 1
+
+
+def token_key(key: int, t: int) -> int:
+    """The sampler key of the ``t``-th new token of a call (63 bits: a signed operator argument).
+    ``sample_dev_`` (csrc/kernels/decode.hip) forms the same number on the device."""
+    return (int(key) + (int(t) + 1) * 0x9E3779B97F4A7C15) & _MASK63
 
 
 def uniforms(key: int, step: int, rows: int, row0: int = 0) -> np.ndarray:
