@@ -65,6 +65,13 @@ def build_checkpoint(model, optimizer, lr_scheduler, training_step: int, host: D
     }
     if rng is not None:
         out["rng"] = rng
+    if "ema" in host:
+        # --ema-decay: the parameter average under the model's keys, fp32 views of one flat buffer
+        # like the moments (files written without the flag have neither entry)
+        E = host["ema"]
+        out["ema"] = OrderedDict((name, _view(E, flat.slots[name])) for name in model_sd)
+        meta["ema"] = {"decay": float(optimizer.ema_decay), "every": int(optimizer.ema_every),
+                       "updates": int(optimizer.ema_updates)}
     return out
 
 
@@ -106,6 +113,15 @@ def restore_model(model, sd: Dict[str, torch.Tensor]) -> str:
     for name in expected:
         _view(flat.params, flat.slots[name]).copy_(sd[name], non_blocking=True)
     return "per-tensor"
+
+
+def state_buffers(model, optimizer) -> Dict[str, torch.Tensor]:
+    """The whole flat state buffers of a single-writer engine, by the names of the digest record:
+    parameters, both moments and, under --ema-decay, the parameter average."""
+    out = {"params": model.flat.params, "exp_avg": optimizer.exp_avg, "exp_avg_sq": optimizer.exp_avg_sq}
+    if getattr(optimizer, "ema", None) is not None:
+        out["ema"] = optimizer.ema
+    return out
 
 
 def capture_rng(device: torch.device) -> Dict[str, Any]:
@@ -150,4 +166,10 @@ def shard_regions(model, optimizer, rank: int, world: int, align: int = 2048):
     else:
         for name, buf in (("exp_avg", optimizer.exp_avg), ("exp_avg_sq", optimizer.exp_avg_sq)):
             regions.append(Region(name, buf[lo:hi], [(lo, 0, hi - lo)], P))
+    ema = getattr(optimizer, "ema", None)
+    if ema is not None:  # --ema-decay: sharded like the moments
+        if optimizer.zero1:
+            regions.append(Region("ema", ema, pieces, P))
+        else:
+            regions.append(Region("ema", ema[lo:hi], [(lo, 0, hi - lo)], P))
     return regions

@@ -1,7 +1,8 @@
 """Checkpoint state digests: the record a save puts into the file, and the checks against it.
 
 Every checkpoint the engine writes carries a ``state_digest`` record beside ``data.pkl``: for each
-flat state buffer (parameters, ``exp_avg``, ``exp_avg_sq``) the position-weighted exact digest of
+flat state buffer (parameters, ``exp_avg``, ``exp_avg_sq`` and, under ``--ema-decay``, ``ema``) the
+position-weighted exact digest of
 :mod:`..utils.digest`, formed on the device from the snapshot the file was written from. A resume
 digests the buffers where they live after the restore and refuses to train on a mismatch
 (:func:`verify_restored`, :class:`CheckpointCorrupt`): a flipped bit, a short or misdirected write

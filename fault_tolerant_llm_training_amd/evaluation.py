@@ -145,14 +145,26 @@ def run_evaluation(model, eval_set: EvalSet, device: torch.device, group=None,
     return out, None
 
 
-def metrics_record(step: int, s: dict) -> dict:
-    return {"eval_step": step, "eval_loss": s["loss"], "eval_loss_fx": s["loss_fx"], "eval_tokens": s["tokens"],
-            "eval_correct": s["correct"], "eval_nonfinite": s["nonfinite"], "eval_s": s["seconds"]}
+def metrics_record(step: int, s: dict, ema: Optional[dict] = None) -> dict:
+    """``ema``: the summary of the same set on the averaged weights (--eval-ema), added as ``ema_*``
+    fields; the other fields are those of a record without it."""
+    rec = {"eval_step": step, "eval_loss": s["loss"], "eval_loss_fx": s["loss_fx"], "eval_tokens": s["tokens"],
+           "eval_correct": s["correct"], "eval_nonfinite": s["nonfinite"], "eval_s": s["seconds"]}
+    if ema is not None:
+        rec.update(ema_loss=ema["loss"], ema_loss_fx=ema["loss_fx"], ema_perplexity=ema["perplexity"],
+                   ema_accuracy=ema["accuracy"], ema_correct=ema["correct"], ema_nonfinite=ema["nonfinite"],
+                   ema_s=ema["seconds"])
+    return rec
 
 
-def log_line(step: int, s: dict) -> str:
+def log_line(step: int, s: dict, ema: Optional[dict] = None) -> str:
     line = (f"Evaluation at step {step} | Loss: {s['loss']:.4f} | Perplexity: {s['perplexity']:.2f} | "
             f"Accuracy: {s['accuracy']:.4f} | Tokens: {s['tokens']} | {s['seconds']:.2f}s")
     if s["nonfinite"]:
         line += f" | Non-finite rows left out: {s['nonfinite']}"
+    if ema is not None:
+        line += (f" | ema_loss: {ema['loss']:.4f} | ema_perplexity: {ema['perplexity']:.2f} | "
+                 f"ema_accuracy: {ema['accuracy']:.4f} | ema_s: {ema['seconds']:.2f}")
+        if ema["nonfinite"]:
+            line += f" | ema_nonfinite: {ema['nonfinite']}"
     return line

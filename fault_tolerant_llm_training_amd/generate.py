@@ -13,6 +13,9 @@ weights per token for all rows): ``--json`` then prints one line per row with a 
 text mode a line ``--- sample b ---`` before each row. One row without these flags prints what it
 always printed.
 
+``--use-ema`` reads the ``ema`` entry of a ``--ema-decay`` run instead of ``model``: the fp32 parameter
+average, rounded to nearest in ``--model-dtype``.
+
 ``--decode-graph`` decodes with ``generation.DecodeGraph``: one captured HIP graph per token, replayed,
 instead of about nine launches per layer issued from Python. The ids are the same.
 """
@@ -51,9 +54,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
     p.add_argument("--top-k", type=int, default=0, help="0: all tokens")
     p.add_argument("--seed", type=int, default=1234, help="Seed of the sampler key")
+    p.add_argument("--sampler-step", type=int, default=0,
+                   help="Step of the stateless sampler (default 0); train.py's --sample-every samples use the "
+                   "training step, so the boundary's step reproduces its sample from that step's checkpoint")
     p.add_argument("--decode-graph", action="store_true",
                    help="Decode by replaying one captured HIP graph per token instead of launching every kernel "
                    "from Python (the same ids; GPU models of a kernel dtype with a vocabulary that is a multiple of 8, elsewhere ignored)")
+    p.add_argument("--use-ema", action="store_true",
+                   help="Generate from the file's `ema` entry (the parameter average of a --ema-decay run), rounded "
+                   "to nearest in --model-dtype, instead of `model`; an error if the file has none")
     p.add_argument("--json", action="store_true", help="Print one JSON line instead of the text")
     return p
 
@@ -145,9 +154,15 @@ def main(argv=None) -> int:
                       "vocab_size") if f in rec and rec[f] != getattr(margs, f)]
     if diff:  # before anything is allocated for the wrong architecture
         return _fail(f"{args.checkpoint} does not fit --model {args.model} with vocabulary {vocab} ({'; '.join(diff)})")
+    entry = "model"
+    if args.use_ema:
+        if not isinstance(ckpt.get("ema"), dict):
+            return _fail(f"{args.checkpoint} has no ema entry (it was written without --ema-decay); "
+                         "drop --use-ema to generate from its model entry")
+        entry = "ema"  # fp32 tensors: restore_model's per-tensor copies round them to nearest in --model-dtype
     try:
         model = build_model(margs, device, dtype)
-        restore_model(model, ckpt["model"])
+        restore_model(model, ckpt[entry])
     except Exception as e:  # noqa: BLE001 - a layout mismatch: keys, shapes or sizes
         return _fail(f"{args.checkpoint} does not fit --model {args.model} with vocabulary {vocab}: "
                      f"{type(e).__name__}: {str(e).splitlines()[0] if str(e) else ''}")
@@ -160,10 +175,12 @@ def main(argv=None) -> int:
     try:
         if batched:
             rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                                  key=key_from_seed(args.seed), eos_id=eos, graph=args.decode_graph)
+                                  key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
+                                  graph=args.decode_graph)
         else:
             ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
-                           key=key_from_seed(args.seed), eos_id=eos, graph=args.decode_graph)
+                           key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
+                           graph=args.decode_graph)
     except ValueError as e:
         return _fail(str(e))
     dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished

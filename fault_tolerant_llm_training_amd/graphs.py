@@ -49,6 +49,10 @@ class GraphedStep:
             # would replay one step's noise for ever
             raise ValueError("stochastic rounding (--stochastic-rounding) is not supported under "
                              "whole-step graph replay (--hip-graph / --compile)")
+        if getattr(optimizer, "ema", None) is not None and optimizer.ema_every != 1:
+            # the EMA launch is captured with the optimizer: it runs at every replay
+            raise ValueError("--ema-every above 1 is not supported under whole-step graph replay "
+                             "(--hip-graph / --compile)")
         self.model, self.red, self.opt, self.sched = model, reducer, optimizer, lr_scheduler
         self.fwd_bwd = fwd_bwd
         self.graph: Optional[torch.cuda.CUDAGraph] = None

@@ -34,6 +34,7 @@ leaves behind (reference utils.py:61, train.py:107-109).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import List, Optional, Tuple
 
@@ -91,7 +92,8 @@ class FlatAdamW(torch.optim.Optimizer):
     def __init__(self, params, flat: FlatParamSpace, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 1e-2, state_dtype: Optional[torch.dtype] = None,
                  max_grad_norm: float = 0.0, fused: bool = True, reducer=None,
-                 stochastic_rounding: bool = False, sr_seed: int = 0):
+                 stochastic_rounding: bool = False, sr_seed: int = 0, ema_decay: float = 0.0,
+                 ema_every: int = 1):
         params = list(params)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False,
                         maximize=False, foreach=None, capturable=False, differentiable=False,
@@ -138,6 +140,23 @@ class FlatAdamW(torch.optim.Optimizer):
         # parameter index (reference order) -> flat slot
         name_of = {id(p): n for n, p in flat.param_objs.items()}
         self._index_slots = [flat.slots[name_of[id(p)]] for p in params]
+        # --ema-decay: an exponential moving average of the parameters in a fourth flat buffer with the
+        # layout and sharding of exp_avg, fp32 whatever the model dtype (utils/ema.py: at d = 0.999 the
+        # increment is far below half a bf16 spacing). Updated every ema_every optimizer steps with
+        # d ** ema_every, behind each bucket's AdamW launch; read-only to training.
+        from ..utils import ema as _ema
+
+        _ema.check(ema_decay, ema_every)
+        self.ema_decay, self.ema_every = float(ema_decay), int(ema_every)
+        self.ema: Optional[torch.Tensor] = None
+        self._ema_omd = 0.0
+        self._ema_base = (0, 0)  # (step_count, ema_updates) when the average was last set
+        self._ema_event = None   # after the last EMA launch of a pipelined step (side stream)
+        self.pending_step = None  # trainer hook: completes a pending graph optimizer step
+        if self.ema_decay > 0:
+            self.ema = torch.empty(n, dtype=_ema.ema_dtype(flat.dtype), device=flat.device)
+            self._ema_omd = _ema.one_minus_decay(self.ema_decay, self.ema_every, self.ema.dtype)
+            self.reset_ema()
 
     # ------------------------------------------------------------------ step
     def clip_grad_norm_(self, max_norm: Optional[float] = None) -> torch.Tensor:
@@ -151,8 +170,6 @@ class FlatAdamW(torch.optim.Optimizer):
         r = self.reducer
         if r is not None and r.overlap:
             return torch.cuda.stream(r.side)
-        import contextlib
-
         return contextlib.nullcontext()
 
     def _hyper(self):
@@ -192,6 +209,83 @@ class FlatAdamW(torch.optim.Optimizer):
             _adamw_reference(p, g, m, v, self.stats, lr, b1, b2, eps, wd, self.step_count,
                              sr=(self.sr_key, offset) if self.stochastic_rounding else None)
 
+    # ------------------------------------------------------------------ parameter average
+    @torch.no_grad()
+    def reset_ema(self, updates: int = 0) -> None:
+        """Start the average from the parameters as they are now (ZeRO-1: this rank's shards)."""
+        if self.zero1:
+            r = self.reducer
+            for b in r.buckets:
+                slo, shi = r.state_range(b)
+                self.ema[slo:shi].copy_(r.param_shard(b))
+        else:
+            self.ema.copy_(self.flat.params)
+        self._ema_base = (self.step_count, int(updates))
+
+    @property
+    def ema_updates(self) -> int:
+        """Updates the average has taken: a function of the step counter, so it rolls back with it."""
+        s0, u0 = self._ema_base
+        return u0 + self.step_count // self.ema_every - s0 // self.ema_every
+
+    def _ema_due(self) -> bool:
+        if self.ema is None:
+            return False
+        if self.graph_mode and self.ema_every != 1:  # the launch is captured: it would run at every replay
+            raise RuntimeError("ema_every > 1 is not supported under whole-step graph replay")
+        return self.step_count % self.ema_every == 0
+
+    def _ema_update(self, p: torch.Tensor, e: torch.Tensor, max_blocks: int = 0) -> None:
+        """One EMA launch over a piece of the flat buffers (skipped on device like the AdamW launch
+        when the sticky non-finite flag is set)."""
+        if native(p):
+            kernels().ema_update_(e, p, self.stats, self._ema_omd, max_blocks)
+        elif self.stats[2].item() == 0:
+            from ..utils.ema import ema_update_
+
+            ema_update_(e, p, self._ema_omd)
+
+    def wait_ema(self) -> None:
+        """Make the current stream wait for the last step's EMA launches: they follow the events
+        the gate hands out, so ``gate.wait_all()`` alone does not cover them (checkpoint snapshots,
+        digests, :meth:`ema_weights`)."""
+        if self._ema_event is not None:
+            torch.cuda.current_stream().wait_event(self._ema_event)
+            self._ema_event = None
+
+    @torch.no_grad()
+    def _ema_to_params(self) -> None:
+        """flat.params <- the average, rounded to nearest in the model dtype (ZeRO-1: every rank
+        casts its own shards, then the buckets are all-gathered as the parameters are)."""
+        f, r = self.flat, self.reducer
+        if not self.zero1:
+            f.params.copy_(self.ema)
+            return
+        for b in sorted(r.buckets, key=lambda b: b.lo):
+            slo, shi = r.state_range(b)
+            r.param_shard(b).copy_(self.ema[slo:shi])
+            dist.all_gather_into_tensor(f.params[b.lo : b.hi], r.param_shard(b), group=r.group)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the model on the average: inside the context ``flat.params`` holds the average cast
+        to the model dtype; on exit the training weights are back bit for bit. Every rank enters and
+        leaves together (ZeRO-1 all-gathers). Nothing else is written."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights() needs ema_decay > 0")
+        if self.pending_step is not None:
+            self.pending_step()  # graph mode: the last backward's optimizer step, as before a checkpoint
+        self.gate.wait_all()
+        self.wait_ema()
+        saved = self.flat.params.clone()
+        try:
+            self._ema_to_params()
+            yield self
+        finally:
+            with torch.no_grad():
+                self.flat.params.copy_(saved)
+            del saved
+
     @torch.no_grad()
     def step(self, closure=None):
         self.step_count += 1
@@ -199,6 +293,7 @@ class FlatAdamW(torch.optim.Optimizer):
         f = self.flat
         r = self.reducer
         cuda = f.params.is_cuda
+        ema_due = self._ema_due()
         if r is None:
             # stand-alone: whole-buffer norm + one AdamW launch on the current stream
             if cuda:
@@ -211,6 +306,8 @@ class FlatAdamW(torch.optim.Optimizer):
                 gd = f.grads.double() if f.grads.dtype == torch.float64 else f.grads.float()
                 _norm_reference(gd.pow(2).sum().reshape(1), self.stats, self.max_grad_norm)
             self._update(f.params, f.grads, self.exp_avg, self.exp_avg_sq, lr, b1, b2, eps, wd)
+            if ema_due:
+                self._ema_update(f.params, self.ema)
             self._publish_stats()
             return None
         if r.overlap:
@@ -247,6 +344,15 @@ class FlatAdamW(torch.optim.Optimizer):
                 elif r.overlap:
                     b.event.record()
                     self.gate.add(b.lo, b.hi, b.event)
+                if ema_due:
+                    # behind the gate event / all-gather: the next forward never waits for the
+                    # average; the bucket's next AdamW launch follows it on this stream
+                    self._ema_update(r.param_for_update(b), self.ema[slo:shi],
+                                     self.overlap_blocks if r.overlap else 0)
+            if ema_due and r.overlap and not self.graph_mode:  # (a replay joins the side stream itself)
+                if self._ema_event is None:
+                    self._ema_event = torch.cuda.Event()
+                self._ema_event.record()
         return None
 
     def _publish_stats(self):
@@ -419,6 +525,34 @@ class FlatAdamW(torch.optim.Optimizer):
             for k, v in sg.items():
                 if k != "params":
                     g[k] = v
+
+    @torch.no_grad()
+    def load_ema(self, ema_sd, updates: int = 0) -> None:
+        """Restore the average from a checkpoint's ``ema`` entry (the ``model`` keys -> tensors; views
+        of one flat buffer in our files), onto this rank's shards under ZeRO-1. Call after
+        :meth:`load_state_dict`: the update counter continues from the restored step count."""
+        from ..ckpt.format import strip_compile_prefix
+        from ..ckpt.restore import h2d
+        from ..ckpt.state import _flat_source
+
+        slots = self.flat.slots
+        sd = strip_compile_prefix(ema_sd)
+        missing = [k for k in slots if k not in sd]
+        unexpected = [k for k in sd if k not in slots]
+        if missing or unexpected:
+            raise KeyError(f"checkpoint/model mismatch in the ema entry: missing={missing[:5]} "
+                           f"unexpected={unexpected[:5]}")
+        src = _flat_source(sd, slots, self.flat.numel, self.ema.dtype)
+        if src is None:
+            src = torch.zeros(self.flat.numel, dtype=self.ema.dtype)
+            for name, s in slots.items():
+                src[s.offset : s.offset + s.numel].view(s.shape).copy_(sd[name])
+        if self.zero1:
+            for flo, slo, n in self.shard_pieces():
+                h2d(self.ema[slo : slo + n], src[flo : flo + n])
+        else:
+            h2d(self.ema, src)
+        self._ema_base = (self.step_count, int(updates))
 
     def moments(self):
         return self.exp_avg, self.exp_avg_sq

@@ -38,7 +38,7 @@ import torch
 
 from .ckpt.engine import CheckpointEngine
 from .ckpt.format import checkpoint_file, load_checkpoint
-from .ckpt.state import build_checkpoint, capture_rng, restore_model, restore_rng, shard_regions
+from .ckpt.state import build_checkpoint, capture_rng, restore_model, restore_rng, shard_regions, state_buffers
 from .data.loader import IterableSource, MapSource, SyntheticSource, TrainLoader
 from .data.synthetic import SyntheticTokens
 from .ft.exit_handler import classify_exception, handle_exit
@@ -325,8 +325,12 @@ def train(args) -> int:
         raise ValueError("--stochastic-rounding supports bf16 parameters only (--model-dtype bf16)")
     optimizer = FlatAdamW(model.parameters(), model.flat, lr=args.learning_rate, state_dtype=state_dtype,
                           max_grad_norm=args.grad_max_norm, fused=args.fused_optimizer, reducer=reducer,
-                          stochastic_rounding=sr_on, sr_seed=args.seed)
+                          stochastic_rounding=sr_on, sr_seed=args.seed,
+                          ema_decay=float(getattr(args, "ema_decay", 0.0) or 0.0),
+                          ema_every=int(getattr(args, "ema_every", 1) or 1))
     model.gate = optimizer.gate
+    ema_on = optimizer.ema is not None
+    ema_restored = False  # the average came from the file: its digest is verified with the others
     if sr_on:
         recorded = (checkpoint.get("meta") or {}).get("sr_key") if checkpoint is not None else None
         if recorded is not None:
@@ -345,6 +349,30 @@ def train(args) -> int:
     if checkpoint is not None:
         optimizer.load_state_dict(checkpoint["optimizer"])
         logger.info("Optimizer loaded from checkpoint")
+        rec_ema = (checkpoint.get("meta") or {}).get("ema") or {}
+        if ema_on and "ema" in checkpoint:
+            optimizer.load_ema(checkpoint["ema"], updates=int(rec_ema.get("updates", 0)))
+            ema_restored = True
+            logger.info(f"Parameter EMA loaded from checkpoint ({optimizer.ema_updates} updates)")
+            changed = [f"{k} {rec_ema[k]} -> {v}" for k, v in (("decay", optimizer.ema_decay),
+                                                              ("every", optimizer.ema_every))
+                       if k in rec_ema and rec_ema[k] != v]
+            if changed:
+                logger.info("Parameter EMA: settings differ from the checkpoint's (" + ", ".join(changed)
+                            + "); continuing the restored average with the new ones")
+        elif ema_on:
+            optimizer.reset_ema()  # (the step counter was just restored: updates count from here)
+            logger.info("Parameter EMA: the checkpoint has no ema entry (written without --ema-decay); "
+                        "the average starts from the restored parameters with 0 updates")
+        elif "ema" in checkpoint:
+            logger.info("Parameter EMA: the checkpoint has an ema entry but --ema-decay is not set; "
+                        "the entry is ignored (checkpoints of this job carry none)")
+    if ema_on:
+        logger.info(f"Parameter EMA: on -- decay {optimizer.ema_decay:g} per step, updated every "
+                    f"{optimizer.ema_every} optimizer step(s) with 1 - d^K = {optimizer._ema_omd:.9g}; "
+                    f"{optimizer.ema.dtype} buffer of {optimizer.ema.numel()} elements "
+                    f"({optimizer.ema.numel() * optimizer.ema.element_size() / 2**30:.3f} GiB"
+                    + ("/rank, sharded like the AdamW moments" if optimizer.zero1 else "") + ")")
     lr_scheduler = build_lr_scheduler(optimizer, args.lr_warmup_steps)
     if checkpoint is not None:
         lr_scheduler.load_state_dict(checkpoint["lr_scheduler"])
@@ -367,13 +395,25 @@ def train(args) -> int:
         # the last step's AdamW buckets run on the optimizer stream; nothing after the final step
         # makes this stream wait for them, and the digest kernel is quick enough to overtake them
         optimizer.gate.wait_all()
+        optimizer.wait_ema()
         dg = state_digest(model.flat.params, optimizer.exp_avg, optimizer.exp_avg_sq)
         # the loader position a checkpoint at this step boundary records (the live loader may
         # already have fetched the next batch when a signal stops the run)
         pos = loader_at.get(step, loader.state_dict())
         logger.info(f"[rank {info.rank}] State digest at step {step}{when}: params={dg['params']} "
                     f"exp_avg={dg['exp_avg']} exp_avg_sq={dg['exp_avg_sq']} "
+                    + (f"ema={ema_digest()} " if ema_on else "") +
                     f"optimizer_step={optimizer.step_count} data_loader={json.dumps(pos, sort_keys=True)}")
+
+    def ema_digest() -> str:
+        """This rank's digest of the average (ZeRO-1: of its shards, at their flat positions)."""
+        from .utils.digest import MASK64, digest_int
+
+        if optimizer.zero1:
+            v = sum(digest_int(optimizer.ema[slo : slo + n], flo) for flo, slo, n in optimizer.shard_pieces())
+        else:
+            v = digest_int(optimizer.ema, 0)
+        return f"{v & MASK64:016x}"
 
     def verify_resumed_state() -> None:
         """The restored buffers, digested where they now live, against the digest record of the
@@ -386,11 +426,15 @@ def train(args) -> int:
             # every rank digests its own pieces (ZeRO-1: the shards it owns); the partial digests
             # add up over the gloo control group, so all ranks see one value and leave together
             regions = shard_regions(model, optimizer, info.rank, info.world_size)
+            if not ema_restored:  # an average that starts from the parameters has no entry to check
+                regions = [r for r in regions if r.name != "ema"]
             live = {r.name: [(r.data[off : off + n], lo) for lo, off, n in r.pieces] for r in regions}
             numels = {r.name: r.full_numel for r in regions}
             group = info.ctrl_group
         else:
-            live = {"params": model.flat.params, "exp_avg": optimizer.exp_avg, "exp_avg_sq": optimizer.exp_avg_sq}
+            live = state_buffers(model, optimizer)
+            if not ema_restored:
+                live.pop("ema", None)
             numels, group = None, None
         try:
             ok = verify_restored(record, live, group=group, path=resume_file, numels=numels, log=logger.info)
@@ -474,7 +518,7 @@ def train(args) -> int:
                                                   sharded=True, digest=ckpt_digest)
             else:
                 ckpt["engine"] = CheckpointEngine(
-                    {"params": model.flat.params, "exp_avg": optimizer.exp_avg, "exp_avg_sq": optimizer.exp_avg_sq},
+                    state_buffers(model, optimizer),
                     mode=args.checkpoint_mode, writer_threads=args.checkpoint_writer_threads, digest=ckpt_digest)
         return ckpt["engine"]
 
@@ -487,6 +531,7 @@ def train(args) -> int:
     def save_checkpoint(blocking: bool, step_now: int):
         """Collective save of the state at step boundary ``step_now`` (every rank calls it)."""
         optimizer.gate.wait_all()  # the snapshot must follow this step's parameter updates
+        optimizer.wait_ema()  # ... and its EMA launches, which run behind the gate's events
         states = fdist.ctrl_all_gather_object(loader_at.get(step_now, loader.state_dict()))
         rng = capture_rng(device)
 
@@ -525,8 +570,7 @@ def train(args) -> int:
                                     data_loader=states if info.distributed else states[0], rng=rng,
                                     extra_meta=dict(run_meta))
 
-        solo = CheckpointEngine({"params": model.flat.params, "exp_avg": optimizer.exp_avg,
-                                 "exp_avg_sq": optimizer.exp_avg_sq}, mode="host",
+        solo = CheckpointEngine(state_buffers(model, optimizer), mode="host",
                                 writer_threads=args.checkpoint_writer_threads, digest=ckpt_digest)
         # (the lock file stays: a slower survivor must not write the file a second time)
         return solo.save(ckpt_path, build, step=step_now, blocking=True)
@@ -614,6 +658,10 @@ def train(args) -> int:
 
     eval_every = int(getattr(args, "eval_every", 0) or 0)
     eval_set = None
+    eval_ema = bool(getattr(args, "eval_ema", False))
+    sample_ema = bool(getattr(args, "sample_ema", False))
+    if (eval_ema or sample_ema) and not ema_on:
+        raise ValueError("--eval-ema / --sample-ema need --ema-decay")
     if eval_every > 0:
         from . import evaluation
 
@@ -629,9 +677,20 @@ def train(args) -> int:
         nonlocal pending_err
         complete_pending()  # graph mode: the parameters of this boundary exist after the pending optimizer step
         logger.info(f"Evaluating at step {step_now}: {eval_set.sequences} sequences")
-        summary, err = evaluation.run_evaluation(
-            model, eval_set, device, group=info.ctrl_group if info.distributed else None,
-            pending_signal=monitor.pending, has_error=lambda: pending_err is not None)
+        def one_pass():
+            return evaluation.run_evaluation(
+                model, eval_set, device, group=info.ctrl_group if info.distributed else None,
+                pending_signal=monitor.pending, has_error=lambda: pending_err is not None)
+
+        summary, err = one_pass()
+        ema_summary = None
+        if summary is not None and eval_ema:
+            # --eval-ema: the same set once more on the averaged weights (every rank enters and leaves
+            # the swap together); the training weights are back, bit for bit, before anything else runs
+            with optimizer.ema_weights():
+                ema_summary, err = one_pass()
+            if ema_summary is None:
+                summary = None
         if summary is None:
             if err is not None:
                 logger.error(f"Evaluation error at step {step_now}: {err!r}")
@@ -641,9 +700,9 @@ def train(args) -> int:
             boundary(final=final)  # the same signal / error columns: every rank stops here together
             raise RuntimeError("an abandoned evaluation did not stop the run")
         if info.is_main:
-            logger.info(evaluation.log_line(step_now, summary))
+            logger.info(evaluation.log_line(step_now, summary, ema_summary))
             if metrics_f is not None:
-                metrics_f.write(json.dumps(evaluation.metrics_record(step_now, summary)) + "\n")
+                metrics_f.write(json.dumps(evaluation.metrics_record(step_now, summary, ema_summary)) + "\n")
                 metrics_f.flush()
 
     stats_every = int(getattr(args, "tensor_stats_every", 0) or 0)
@@ -702,7 +761,7 @@ def train(args) -> int:
                     f"{args.sample_tokens} tokens from a prompt of {len(sample_prompt)} (temperature "
                     f"{args.sample_temperature:g}, top-k {args.sample_top_k}; key {sample_key:#018x} from --seed, "
                     "sampler step = training step); the other ranks wait in the next vote (keep it far below "
-                    "--peer-timeout)")
+                    "--peer-timeout)" + ("; --sample-ema: decoded from the parameter EMA" if sample_ema else ""))
 
     sample_graph = None  # --sample-graph: the run's DecodeGraph, built at the first boundary
 
@@ -730,6 +789,15 @@ def train(args) -> int:
         save, an evaluation and the statistics. Rank 0 alone: the parameters are replicated (ZeRO-1: after
         the all-gather the gate waits for) and generation issues no collective. Read-only."""
         complete_pending()  # graph mode: the parameters of this boundary exist after the pending optimizer step
+        if sample_ema:
+            # --sample-ema: the model runs on the averaged weights while rank 0 decodes; every rank takes
+            # part in the swap (ZeRO-1 all-gathers) and has its training weights back on exit
+            with optimizer.ema_weights():
+                _sample(step_now, " | from the parameter EMA")
+        else:
+            _sample(step_now, "")
+
+    def _sample(step_now: int, origin: str) -> None:
         if not info.is_main:
             return
         nonlocal pending_err
@@ -746,14 +814,14 @@ def train(args) -> int:
         if sample_count > 1:
             texts = [sample_tok.decode(r) if sample_tok is not None else " ".join(str(i) for i in r) for r in rows]
             for b, (r, text) in enumerate(zip(rows, texts)):
-                logger.info(f"Sample {b} at step {step_now} | {text!r} | {len(r)} tokens | {dt:.2f} s")
+                logger.info(f"Sample {b} at step {step_now} | {text!r} | {len(r)} tokens | {dt:.2f} s{origin}")
             if metrics_f is not None:
                 metrics_f.write(json.dumps({"sample_step": step_now, "sample_ids": rows, "sample_text": texts,
                                             "sample_s": dt}) + "\n")
                 metrics_f.flush()
             return
         text = sample_tok.decode(ids) if sample_tok is not None else " ".join(str(i) for i in ids)
-        logger.info(f"Sample at step {step_now} | {text!r} | {len(ids)} tokens | {dt:.2f} s")
+        logger.info(f"Sample at step {step_now} | {text!r} | {len(ids)} tokens | {dt:.2f} s{origin}")
         if metrics_f is not None:
             metrics_f.write(json.dumps({"sample_step": step_now, "sample_ids": ids, "sample_text": text,
                                         "sample_s": dt}) + "\n")
@@ -788,6 +856,8 @@ def train(args) -> int:
             if ckpt["engine"] is not None:
                 ckpt["engine"].fence()
             graphed.finish()
+
+    optimizer.pending_step = complete_pending  # ema_weights(): the swap follows a pending graph step
 
     try:
         while training_step < args.training_steps:

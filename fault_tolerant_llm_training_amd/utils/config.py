@@ -354,6 +354,34 @@ def build_parser() -> argparse.ArgumentParser:
         "multiple of 8 (elsewhere the samples are decoded eagerly)",
     )
     parser.add_argument(
+        "--ema-decay",
+        type=float,
+        default=0.0,
+        help="Keep an exponential moving average of the parameters with this decay per optimizer step "
+        "(0: off; otherwise 0 < D < 1, e.g. 0.999): an fp32 flat buffer updated behind each AdamW launch, "
+        "sharded under ZeRO-1, saved in the checkpoint as the `ema` entry with a digest. Read-only to "
+        "training: parameters, moments and losses are bit-identical to a run without the flag",
+    )
+    parser.add_argument(
+        "--ema-every",
+        type=int,
+        default=1,
+        help="Update the average every K optimizer steps (steps K, 2K, ...) with decay D ** K (default 1). "
+        "K > 1 not with --hip-graph / --compile: the captured launch would run at every replay",
+    )
+    parser.add_argument(
+        "--eval-ema",
+        action="store_true",
+        help="Run each --eval-every evaluation a second time on the averaged weights; its loss, perplexity and "
+        "accuracy are added to the same record as ema_* fields. Needs --eval-every and --ema-decay",
+    )
+    parser.add_argument(
+        "--sample-ema",
+        action="store_true",
+        help="Generate the --sample-every samples from the averaged weights (same sampler key and step). "
+        "Needs --sample-every and --ema-decay",
+    )
+    parser.add_argument(
         "--profile-steps",
         type=str,
         default="",
@@ -382,6 +410,19 @@ def get_args(argv=None) -> argparse.Namespace:
     if args.stochastic_rounding and (args.hip_graph or args.compile):
         parser.error("--stochastic-rounding is not supported under whole-step graph replay "
                      "(--hip-graph / --compile): run the step eagerly")
+    if not (args.ema_decay == 0.0 or 0.0 < args.ema_decay < 1.0):
+        parser.error(f"--ema-decay must be 0 (off) or in (0, 1), got {args.ema_decay}")
+    if args.ema_every < 1:
+        parser.error(f"--ema-every must be >= 1, got {args.ema_every}")
+    if args.ema_every > 1 and args.ema_decay == 0.0:
+        parser.error("--ema-every needs --ema-decay")
+    if args.ema_decay > 0 and args.ema_every > 1 and (args.hip_graph or args.compile):
+        parser.error("--ema-every above 1 is not supported under whole-step graph replay (--hip-graph / "
+                     "--compile): the captured update would run at every replay; use --ema-every 1")
+    if args.eval_ema and not (args.eval_every > 0 and args.ema_decay > 0):
+        parser.error("--eval-ema needs --eval-every and --ema-decay")
+    if args.sample_ema and not (args.sample_every > 0 and args.ema_decay > 0):
+        parser.error("--sample-ema needs --sample-every and --ema-decay")
     if args.eval_every < 0:
         parser.error(f"--eval-every must be >= 0, got {args.eval_every}")
     if args.tensor_stats_every < 0:
