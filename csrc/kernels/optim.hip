@@ -85,8 +85,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(typename P::T* __restrict__ 
                                                     const typename P::T* __restrict__ g,
                                                     typename S::T* __restrict__ m,
                                                     typename S::T* __restrict__ v,
-                                                    long n8, float lr, float beta1, float beta2,
-                                                    float eps, float wd, float inv_bc1,
+                                                    long n8, float lr, float omb1, float beta2,
+                                                    float omb2, float eps, float wd, float inv_bc1,
                                                     float inv_sqrt_bc2,
                                                     const float* __restrict__ stats,
                                                     const float* __restrict__ hyper, int exact,
@@ -113,8 +113,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(typename P::T* __restrict__ 
     for (int j = 0; j < 8; ++j) {
       const float gj = gf[j] * coef;
       pf[j] *= decay;
-      mf[j] += (gj - mf[j]) * (1.f - beta1);
-      vf[j] = vf[j] * beta2 + (1.f - beta2) * gj * gj;
+      mf[j] += (gj - mf[j]) * omb1;
+      vf[j] = vf[j] * beta2 + omb2 * gj * gj;
       if (exact) {  // IEEE division / sqrt (FT_EXACT_MATH A/B)
         const float denom = sqrtf(vf[j]) * inv_sqrt_bc2 + eps;
         pf[j] -= step * mf[j] / denom;
@@ -240,9 +240,13 @@ void adamw_(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const
               "adamw: dtype mismatch");
   const at::DeviceGuard guard(p.device());
   const long n8 = p.numel() / 8;
-  const float bc1 = 1.f - (float)std::pow(beta1, (double)step);
-  const float bc2 = 1.f - (float)std::pow(beta2, (double)step);
-  const float inv_bc1 = 1.f / bc1, inv_sqrt_bc2 = 1.f / std::sqrt(bc2);
+  // The scalars are formed in double and rounded once, like torch AdamW's: in fp32, 1.f - 0.999f is
+  // 1.3e-5 off and 1.f - (float)beta2^step as much at small steps, which on elements whose stored v
+  // is near zero moved the update by more than fp32 rounding (tests/test_dtypes_gpu.py).
+  const double bc1 = 1.0 - std::pow(beta1, (double)step);
+  const double bc2 = 1.0 - std::pow(beta2, (double)step);
+  const float inv_bc1 = (float)(1.0 / bc1), inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
+  const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);  // 1 - beta
   int nb = stream_grid(n8);
   // max_blocks > 0 overrides the default grid cap (both directions): small grids
   // leave CUs to a concurrent stream, large ones make every block short-lived so
@@ -265,13 +269,13 @@ void adamw_(const at::Tensor& p, const at::Tensor& g, const at::Tensor& m, const
     constexpr bool SR = decltype(srtag)::value;
     if (nt)
       hipLaunchKernelGGL((adamw_kernel<P, S, true, SR>), grid, block, 0, ft_stream(), mptr<PT>(p),
-                         cptr<PT>(g), mptr<ST>(m), mptr<ST>(v), n8, (float)lr, (float)beta1,
-                         (float)beta2, (float)eps, (float)wd, inv_bc1, inv_sqrt_bc2,
+                         cptr<PT>(g), mptr<ST>(m), mptr<ST>(v), n8, (float)lr, omb1,
+                         (float)beta2, omb2, (float)eps, (float)wd, inv_bc1, inv_sqrt_bc2,
                          cptr<float>(stats), hp, exact, sr);
     else
       hipLaunchKernelGGL((adamw_kernel<P, S, false, SR>), grid, block, 0, ft_stream(), mptr<PT>(p),
-                         cptr<PT>(g), mptr<ST>(m), mptr<ST>(v), n8, (float)lr, (float)beta1,
-                         (float)beta2, (float)eps, (float)wd, inv_bc1, inv_sqrt_bc2,
+                         cptr<PT>(g), mptr<ST>(m), mptr<ST>(v), n8, (float)lr, omb1,
+                         (float)beta2, omb2, (float)eps, (float)wd, inv_bc1, inv_sqrt_bc2,
                          cptr<float>(stats), hp, exact, sr);
   };
   if (stochastic_rounding) {  // bf16 parameters (checked above); moments bf16 or fp32

@@ -30,6 +30,8 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const typename E::T* __re
 #pragma unroll
     for (int j = 1; j < 8; ++j) lm = fmaxf(lm, x[j]);
     const float nm = fmaxf(m, lm);
+    // all -inf so far: s stays 0 (x - nm would be NaN and poison the row), as in the merge below
+    if (nm == -INFINITY) continue;
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += exp2f((x[j] - nm) * LOG2E);

@@ -71,11 +71,13 @@ __global__ __launch_bounds__(256) void xent_eval_kernel(const typename E::T* __r
 #pragma unroll
       for (int j = 1; j < 8; ++j) lm = fmaxf(lm, x[j]);
       const float nm = fmaxf(m, lm);
-      float a = 0.f;
+      if (nm != -INFINITY) {  // all -inf so far: s stays 0 (x - nm would be NaN), as in the merge below
+        float a = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) a += exp2f((x[j] - nm) * LOG2E);
-      s = __builtin_fmaf(s, exp2f((m - nm) * LOG2E), a);
-      m = nm;
+        for (int j = 0; j < 8; ++j) a += exp2f((x[j] - nm) * LOG2E);
+        s = __builtin_fmaf(s, exp2f((m - nm) * LOG2E), a);
+        m = nm;
+      }
       beat |= lm > xy;
       if (lm == xy && c < yc) {  // a tie with the label: only a lower column wins
 #pragma unroll

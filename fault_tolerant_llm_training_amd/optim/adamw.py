@@ -180,17 +180,16 @@ class FlatAdamW(torch.optim.Optimizer):
     def stage_hyper(self, step: int) -> None:
         """Graph mode: enqueue the H2D copy of [lr, 1/bc1, 1/sqrt(bc2)] of optimizer step
         ``step`` into ``self.hyper`` (on the current stream, ahead of the replay that uses it),
-        rounded to fp32 exactly like the host path of adamw_ (optim.hip): bc = 1.f - (float)beta^step,
-        then 1/bc and 1/sqrtf(bc) in float."""
+        rounded to fp32 exactly like the host path of adamw_ (optim.hip): bc = 1 - beta^step, 1/bc and
+        1/sqrt(bc) in double, each rounded once."""
         import numpy as np
 
         lr, b1, b2, _eps, _wd = self._hyper()
-        bc1 = np.float32(1.0) - np.float32(b1 ** step)  # 1.f - (float)std::pow(beta, step)
-        bc2 = np.float32(1.0) - np.float32(b2 ** step)
+        bc1 = 1.0 - b1 ** step
+        bc2 = 1.0 - b2 ** step
         h = self._hyper_ring[self._hyper_i % len(self._hyper_ring)]
         self._hyper_i += 1
-        h.copy_(torch.from_numpy(np.array([np.float32(lr), np.float32(1.0) / bc1,
-                                           np.float32(1.0) / np.sqrt(bc2)], dtype=np.float32)))
+        h.copy_(torch.from_numpy(np.array([lr, 1.0 / bc1, 1.0 / math.sqrt(bc2)], dtype=np.float32)))
         self.hyper.copy_(h, non_blocking=True)
 
     def _update(self, p, g, m, v, lr, b1, b2, eps, wd, max_blocks: int = 0, offset: int = 0):

@@ -121,13 +121,18 @@ def test_swiglu_xent_embedding(K, dt):
 @pytest.mark.parametrize("pdt,sdt", [(torch.float16, torch.float16), (torch.float16, torch.float32),
                                      (torch.float32, torch.float32)])
 def test_grad_norm_adamw(K, pdt, sdt):
+    """At training scale the fp16 bound sees the host scalars: with 1 - beta2 and the bias corrections formed
+    in fp32 (1.f - 0.999f is 1.3e-5 off) rel(p) was 4.6e-5, on the elements whose stored v is near zero; formed
+    in double and rounded once (optim.hip adamw_), as _adamw_reference and torch AdamW do, the bound holds (a CPU fp32 evaluation of the same formula gives 3.6e-7)."""
     from fault_tolerant_llm_training_amd.optim.adamw import _adamw_reference
 
     n = 1 << 20
-    g = (0.01 * torch.randn(n, device="cuda")).to(pdt)
-    p = torch.randn(n, device="cuda").to(pdt)
-    m = (0.001 * torch.randn(n, device="cuda")).to(sdt)
-    v = (1e-5 * torch.rand(n, device="cuda")).to(sdt)
+    # training scale: every term of the update moves the stored value (tests/test_elementwise_oracle_cpu.py)
+    torch.manual_seed(0)  # the draws no longer depend on which tests ran before
+    g = (1e-3 * torch.randn(n, device="cuda")).to(pdt)
+    p = (0.02 * torch.randn(n, device="cuda")).to(pdt)
+    m = (1e-3 * torch.randn(n, device="cuda")).to(sdt)
+    v = (1e-6 * torch.rand(n, device="cuda")).to(sdt)
     stats = torch.zeros(3, device="cuda")
     K.grad_norm_(g, stats, 1.0)
     ref_norm = g.double().norm().item()

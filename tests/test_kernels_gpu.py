@@ -136,10 +136,12 @@ def test_grad_norm_adamw(K, state_dtype):
     from fault_tolerant_llm_training_amd.optim.adamw import _adamw_reference
 
     n = 1 << 20
-    g = torch.randn(n, device="cuda").bfloat16()
-    p = torch.randn(n, device="cuda").bfloat16()
-    m = (0.1 * torch.randn(n, device="cuda")).to(state_dtype)
-    v = (0.01 * torch.rand(n, device="cuda")).to(state_dtype)
+    # training scale (p ~ 0.02, g ~ m ~ 1e-3, v ~ 1e-6): every term of the update moves the stored
+    # value, so the bounds below notice a missing one (tests/test_elementwise_oracle_cpu.py)
+    g = (1e-3 * torch.randn(n, device="cuda")).bfloat16()
+    p = (0.02 * torch.randn(n, device="cuda")).bfloat16()
+    m = (1e-3 * torch.randn(n, device="cuda")).to(state_dtype)
+    v = (1e-6 * torch.rand(n, device="cuda")).to(state_dtype)
     stats = torch.zeros(3, device="cuda")
     K.grad_norm_(g, stats, 1.0)
     ref_norm = g.float().norm().item()
