@@ -11,7 +11,7 @@
 //   gemv_swiglu         a[H] = silu(w1 x) * (w3 x) from [w1; w3]    one wave per feature, both rows
 //   decode_qkv_append_  RoPE at `pos` on Q (in place) and K (into k_cache[:, pos]); V into v_cache[:, pos]
 //   decode_attn         one query over keys 0 .. n_keys-1 of the cache, GQA indexed in place
-//   sample_             one token per row of logits: greedy, or temperature / top-k sampling
+//   sample_             one token per row of logits: greedy, or temperature / top-k / top-p sampling
 //
 // Batched generation (B sequences per pass over the weights) has a `_rows` form of the first four:
 // gemv_rows, gemv_swiglu_rows, decode_qkv_append_rows_, decode_attn_rows. Each returns for row r the
@@ -21,7 +21,8 @@
 // Reproducibility: nothing on a result path is accumulated with atomics and every reduction has a
 // fixed order (per-lane sweep, xor butterfly over the wave, waves in index order, key chunks in
 // chunk order), so each op returns the same bits from run to run. The sampler's top-k threshold is
-// found with integer histograms in LDS (integer counts do not depend on the order of the adds).
+// found with integer histograms in LDS (integer counts do not depend on the order of the adds), and
+// its top-p threshold with histograms of 64-bit fixed-point weights (integer adds again).
 //
 // Positions, key counts and the sampler's step are host integers (kernel arguments); the `_rows` ops
 // take each row's start position from a device tensor `pos0` plus one host integer `t`.
@@ -33,6 +34,7 @@
 // return the same bits. decode_ctl_advance_ steps the counter in a launch of its own, after every
 // reader of the pass.
 #include <climits>
+#include <type_traits>
 
 #include "sround.h"
 #include "torch_utils.h"
@@ -53,6 +55,7 @@ enum : int {
   CTL_STEP = 3,         // the sampler's step
   CTL_TEMPERATURE = 4,  // float bits
   CTL_TOP_K = 5,
+  CTL_TOP_P = 6,        // float bits; 0 (what a writer that knows no top-p leaves) or >= 1: off
   CTL_WORDS = 8
 };
 
@@ -548,6 +551,24 @@ __global__ __launch_bounds__(D) void decode_attn_merge_rows_dev_kernel(const flo
 //               order-preserving integer image of the logits (NaN lowest, -0 = +0), and how many of
 //               the columns equal to it are taken; then, if not all of them, the column of the last
 //               one taken (ties go to the lower index)
+//   passes P    top-p only (0 < top_p < 1): the nucleus, the shortest prefix of the candidates in
+//               descending order (equal values by ascending column) whose weight reaches top_p * W,
+//               W the candidates' total. Weights are monotone in the logit, so the nucleus has the
+//               form of the top-k set, and a second 4 x 8-bit radix select over the same integer
+//               image finds it, by mass instead of by count: per pass the candidates' weight per
+//               bucket, the buckets walked from the top with the mass still needed carried along.
+//               It ends at a value thr_p with `need` still to cover there; the cnt_eq candidates
+//               equal to it weigh w_thr each, so the n = ceil(need / w_thr) lowest columns of them
+//               are taken, found by the tie scan of passes B.
+//               The masses are 64-bit fixed point, added with integer LDS atomics: a weight
+//               w = expf(.) in [0, 1] becomes rint(w * 2^s), s = 62 - ceil(log2 V), so V weights
+//               cannot overflow 2^62 and every sum is exact whatever the order of the adds. Each
+//               weight is off by at most half a unit, 2^-(s+1), and all of them together by at most
+//               V * 2^-(s+1): at V = 131072, s = 45 and that is 2^17 * 2^-46 = 1.9e-9 (twice that,
+//               3.7e-9, had the weights been truncated), below 1e-8 * W since W >= 1: the row
+//               maximum weighs 1. At smaller V the scale grows and the bound shrinks. W itself is the sum of the
+//               first pass's buckets, so no sweep is spent on it and `need <= W` holds exactly: the
+//               walk always ends in a bucket of positive mass.
 //   pass C      total = sum of the candidates' weights exp((x - max) / temperature): fp32 weights,
 //               summed in fp64 (its rounding is far below the weights' own)
 //   pass D      the first candidate, in column order, whose cumulative weight reaches u * total
@@ -595,16 +616,21 @@ __device__ __forceinline__ int block_min(int v, int* sh) {
 template <class E>
 __device__ __forceinline__ void sample_rows(const typename E::T* __restrict__ logits, int64_t* __restrict__ out,
                                             int64_t* __restrict__ col, long col_stride, int V, int R,
-                                            float temperature, int top_k, uint32_t key_lo, uint32_t key_hi,
-                                            uint32_t step) {
+                                            float temperature, int top_k, float top_p, uint32_t key_lo,
+                                            uint32_t key_hi, uint32_t step) {
   __shared__ float sh_m[4];
   __shared__ int sh_i[4];
   __shared__ double sh_d[4];
   __shared__ int hist[256];
   __shared__ uint32_t s_prefix;
   __shared__ int s_kk, s_cnt, s_tie;
+  __shared__ unsigned long long mass[256];
+  __shared__ unsigned long long s_need;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const bool all = top_k <= 0 || top_k >= V;
+  const bool all_k = top_k <= 0 || top_k >= V;
+  const bool nucleus = top_p > 0.f && top_p < 1.f;
+  // the fixed-point scale of the passes P: 2^(62 - ceil(log2 V))
+  const double fx_scale = (double)(1ull << (62 - (V > 1 ? 32 - __clz(V - 1) : 0)));
   for (int row = blockIdx.x; row < R; row += gridDim.x) {
     const typename E::T* lr = logits + (long)row * V;
     // ---- pass A: the maximum and the lowest column that attains it
@@ -650,7 +676,40 @@ __device__ __forceinline__ void sample_rows(const typename E::T* __restrict__ lo
       }
       continue;
     }
+    // the column of the kk-th (1-based, in column order) of the columns whose key equals `eq_key`
+    // (V where there are fewer than kk of them)
+    auto nth_equal = [&](uint32_t eq_key, int kk) -> int {
+      if (tid == 0) s_tie = V;
+      __syncthreads();
+      int run = 0;
+      for (int c0 = 0; c0 < V; c0 += 2048) {
+        const int c = c0 + tid * 8;
+        uint32_t eq = 0u;
+        if (c < V) {
+          float x[8];
+          ld8<E>(lr + c, x);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) eq |= (okey(x[j]) == eq_key ? 1u : 0u) << j;
+        }
+        const int cnt = __popc(eq);
+        int tot;
+        const int before = run + block_scan<int>(cnt, sh_i, tot);
+        if (before < kk && kk <= before + cnt) {
+          int r = before;
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if ((eq >> j) & 1u) {
+              if (++r == kk) s_tie = c + j;
+            }
+        }
+        run += tot;
+        __syncthreads();
+        if (run >= kk) break;  // uniform: run is the same in every thread
+      }
+      return s_tie;
+    };
     // ---- passes B: candidates are key > thr, or key == thr at a column <= tie_last
+    bool all = all_k;
     uint32_t thr = 0u;
     int tie_last = V;
     if (!all) {
@@ -687,33 +746,93 @@ __device__ __forceinline__ void sample_rows(const typename E::T* __restrict__ lo
         cnt_eq = s_cnt;
       }
       thr = prefix;
-      if (kk < cnt_eq) {  // only the kk lowest columns of those equal to the threshold
-        int run = 0;
-        for (int c0 = 0; c0 < V; c0 += 2048) {
-          const int c = c0 + tid * 8;
-          uint32_t eq = 0u;
-          if (c < V) {
+      if (kk < cnt_eq) tie_last = nth_equal(thr, kk);  // only the kk lowest columns of those equal to it
+    }
+    // ---- passes P: the nucleus, as a new (thr, tie_last) inside the top-k candidates
+    if (nucleus) {
+      const uint32_t thr_k = thr;
+      const int tie_k = tie_last;
+      // the weight of a top-k candidate in fixed point, 0 for every other column
+      auto weight_fx = [&](float x, uint32_t key, int col) -> unsigned long long {
+        if (!(x == x)) return 0ull;
+        if (!all_k && !(key > thr_k || (key == thr_k && col <= tie_k))) return 0ull;
+        return (unsigned long long)__double2ll_rn((double)expf((x - m) / temperature) * fx_scale);
+      };
+      uint32_t prefix = 0u;
+      unsigned long long need = 0ull, m_eq = 0ull;
+      // a bf16 value has 16 low zero bits, so its key's low half is 0x0000 (value >= 0) or 0xffff
+      // (value < 0, whose key is the complement): two passes find the high half, the sign gives the rest
+      constexpr int PASSES = std::is_same<E, EBF16>::value ? 2 : 4;
+      for (int pass = 0; pass < PASSES; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t hi_mask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
+        mass[tid] = 0ull;
+        __syncthreads();
+        {
+          // runs of equal buckets are summed in registers first: one atomic per run
+          int cur_b = 0;
+          unsigned long long cur = 0ull;
+          for (int c = tid * 8; c < V; c += 2048) {
             float x[8];
             ld8<E>(lr + c, x);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) eq |= (okey(x[j]) == thr ? 1u : 0u) << j;
-          }
-          const int cnt = __popc(eq);
-          int tot;
-          const int before = run + block_scan<int>(cnt, sh_i, tot);
-          if (before < kk && kk <= before + cnt) {
-            int r = before;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-              if ((eq >> j) & 1u) {
-                if (++r == kk) s_tie = c + j;
+            for (int j = 0; j < 8; ++j) {
+              const uint32_t key = okey(x[j]);
+              if ((key & hi_mask) != prefix) continue;
+              const unsigned long long w = weight_fx(x[j], key, c + j);
+              const int b = (int)((key >> shift) & 255u);
+              if (b != cur_b) {
+                if (cur != 0ull) atomicAdd(&mass[cur_b], cur);
+                cur_b = b;
+                cur = 0ull;
               }
+              cur += w;
+            }
           }
-          run += tot;
-          __syncthreads();
-          if (run >= kk) break;  // uniform: run is the same in every thread
+          if (cur != 0ull) atomicAdd(&mass[cur_b], cur);
         }
-        tie_last = s_tie;
+        __syncthreads();
+        if (tid == 0) {
+          unsigned long long nd = need;
+          if (pass == 0) {  // W = the sum of every bucket; need = ceil(top_p * W) in [1, W]
+            unsigned long long wsum = 0ull;
+            for (int i = 0; i < 256; ++i) wsum += mass[i];
+            nd = (unsigned long long)ceil((double)top_p * (double)wsum);  // top_p < 1, wsum <= 2^62
+            nd = nd > wsum ? wsum : nd;
+            nd = nd < 1ull ? 1ull : nd;  // wsum == 0 (no ordered weight at all) is caught below
+          }
+          unsigned long long cum = 0ull;
+          int b = 255;
+          for (; b > 0; --b) {
+            if (cum + mass[b] >= nd) break;
+            cum += mass[b];
+          }
+          s_prefix = prefix | ((uint32_t)b << shift);
+          s_need = nd - cum;
+          mass[0] = mass[b];  // the chosen bucket's mass, read back behind the barrier
+        }
+        __syncthreads();
+        prefix = s_prefix;
+        need = s_need;
+        m_eq = mass[0];
+        __syncthreads();
+      }
+      if (PASSES == 2 && !(prefix & 0x80000000u)) prefix |= 0xffffu;
+      // every candidate equal to the threshold weighs w_thr; m_eq is their total
+      const uint32_t ub = (prefix & 0x80000000u) ? (prefix ^ 0x80000000u) : ~prefix;
+      const unsigned long long w_thr =
+          (unsigned long long)__double2ll_rn((double)expf((__uint_as_float(ub) - m) / temperature) * fx_scale);
+      // The walk ends in a bucket of positive mass with 1 <= need <= m_eq = cnt_eq * w_thr, so this
+      // holds for every row with some weight; a row without any (W = 0: no ordered value, or an
+      // infinite maximum, whose weights are NaN) has no nucleus to take and keeps the top-k candidates.
+      if (w_thr > 0ull && m_eq >= w_thr && need >= 1ull && need <= m_eq) {
+        const unsigned long long cnt_eq = m_eq / w_thr;
+        unsigned long long n = (need + w_thr - 1ull) / w_thr;
+        n = n < 1ull ? 1ull : (n > cnt_eq ? cnt_eq : n);
+        const bool at_k = !all_k && prefix == thr_k;
+        thr = prefix;
+        tie_last = n < cnt_eq ? nth_equal(thr, (int)n) : (at_k ? tie_k : V);
+        all = false;
       }
     }
     auto weight = [&](float x, int col) -> float {
@@ -788,8 +907,9 @@ __device__ __forceinline__ void sample_rows(const typename E::T* __restrict__ lo
 template <class E>
 __global__ __launch_bounds__(256) void sample_kernel(const typename E::T* __restrict__ logits,
                                                      int64_t* __restrict__ out, int V, int R, float temperature,
-                                                     int top_k, uint32_t key_lo, uint32_t key_hi, uint32_t step) {
-  sample_rows<E>(logits, out, nullptr, 0, V, R, temperature, top_k, key_lo, key_hi, step);
+                                                     int top_k, float top_p, uint32_t key_lo, uint32_t key_hi,
+                                                     uint32_t step) {
+  sample_rows<E>(logits, out, nullptr, 0, V, R, temperature, top_k, top_p, key_lo, key_hi, step);
 }
 
 // sample_dev_: the sampling arguments from the control block, and the per-token key
@@ -804,8 +924,9 @@ __global__ __launch_bounds__(256) void sample_dev_kernel(const typename E::T* __
   const uint64_t tk = (key + ((uint64_t)(int64_t)t + 1ull) * 0x9E3779B97F4A7C15ull) & 0x7FFFFFFFFFFFFFFFull;
   const float temperature = __int_as_float(ctl[CTL_TEMPERATURE]);
   const int top_k = min(max(ctl[CTL_TOP_K], 0), V);
+  const float top_p = __int_as_float(ctl[CTL_TOP_P]);  // word 0 is 0.f: off, as is anything not in (0, 1)
   int64_t* col = (t >= 0 && t < n_cap) ? out + t : nullptr;
-  sample_rows<E>(logits, tok, col, n_cap, V, R, temperature, top_k, (uint32_t)tk, (uint32_t)(tk >> 32),
+  sample_rows<E>(logits, tok, col, n_cap, V, R, temperature, top_k, top_p, (uint32_t)tk, (uint32_t)(tk >> 32),
                  (uint32_t)ctl[CTL_STEP]);
 }
 
@@ -1069,8 +1190,8 @@ void decode_attn_rows_dev(const at::Tensor& q, const at::Tensor& k_cache, const 
   FT_LAUNCH_CHECK();
 }
 
-// sample_ with (temperature, top_k, key, step) and the token number t read from ctl on the device:
-// row r draws what sample_(logits, ., temperature, top_k, token_key(key, t), step) draws for it, into
+// sample_ with (temperature, top_k, top_p, key, step) and the token number t read from ctl on the device:
+// row r draws what sample_(logits, ., temperature, top_k, token_key(key, t), step, top_p) draws for it, into
 // tok[r] and out[r, t] (out int64 [R, n_cap]).
 void sample_dev_(const at::Tensor& logits, const at::Tensor& ctl, const at::Tensor& tok, const at::Tensor& out) {
   const char* op = "sample_dev_";
@@ -1250,9 +1371,10 @@ at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at:
 int64_t decode_attn_chunk() { return DECODE_CHUNK; }
 
 // out[r] = one token drawn from row r of logits [R, V]; a pure function of
-// (logits, temperature, top_k, key, step, r). temperature 0: the lowest column of the row maximum.
+// (logits, temperature, top_k, top_p, key, step, r). temperature 0: the lowest column of the row maximum.
+// top_p in (0, 1]; 1 (the default) runs no nucleus pass.
 void sample_(const at::Tensor& logits, const at::Tensor& out, double temperature, int64_t top_k, int64_t key,
-             int64_t step) {
+             int64_t step, double top_p) {
   FT_CHECK_CUDA(logits);
   FT_CHECK_MODEL_DTYPE(logits);
   FT_CHECK_CONTIG(logits);
@@ -1267,6 +1389,7 @@ void sample_(const at::Tensor& logits, const at::Tensor& out, double temperature
   TORCH_CHECK(out.numel() == R, "sample_: out shape mismatch");
   TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY, "sample_: temperature must be finite and >= 0");
   TORCH_CHECK(top_k >= 0, "sample_: top_k must be >= 0 (0: all columns)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0 && (float)top_p > 0.f, "sample_: top_p must be in (0, 1]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "sample_: logits must be 16-byte aligned");
   const at::DeviceGuard guard(logits.device());
   const uint64_t k64 = (uint64_t)key;
@@ -1274,8 +1397,8 @@ void sample_(const at::Tensor& logits, const at::Tensor& out, double temperature
     FT_DISPATCH_E(logits.scalar_type(),
                   hipLaunchKernelGGL(sample_kernel<E>, dim3((unsigned)std::min<int64_t>(R, SAMPLE_MAX_BLOCKS)), dim3(256),
                                      0, ft_stream(), cptr<typename E::T>(logits), mptr<int64_t>(out), (int)V, (int)R,
-                                     (float)temperature, (int)std::min<int64_t>(top_k, V), (uint32_t)k64,
-                                     (uint32_t)(k64 >> 32), (uint32_t)(uint64_t)step));
+                                     (float)temperature, (int)std::min<int64_t>(top_k, V), (float)top_p,
+                                     (uint32_t)k64, (uint32_t)(k64 >> 32), (uint32_t)(uint64_t)step));
   FT_LAUNCH_CHECK();
 }
 
@@ -1294,7 +1417,9 @@ TORCH_LIBRARY_FRAGMENT(ftamd, m) {
         &decode_qkv_append_rows_);
   m.def("decode_attn_rows(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos0, int t, int max_keys) -> Tensor",
         &decode_attn_rows);
-  m.def("sample_(Tensor logits, Tensor(a!) out, float temperature, int top_k, int key, int step) -> ()", &sample_);
+  m.def("sample_(Tensor logits, Tensor(a!) out, float temperature, int top_k, int key, int step, "
+        "float top_p=1.0) -> ()",
+        &sample_);
   m.def("decode_qkv_append_rows_dev_(Tensor(a!) qkv, Tensor cos, Tensor sin, Tensor pos0, Tensor ctl, "
         "Tensor(b!) k_cache, Tensor(c!) v_cache) -> ()",
         &decode_qkv_append_rows_dev_);

@@ -53,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max-new-tokens", type=int, default=64)
     p.add_argument("--temperature", type=float, default=0.0, help="0: greedy")
     p.add_argument("--top-k", type=int, default=0, help="0: all tokens")
+    p.add_argument("--top-p", type=float, default=1.0,
+                   help="Nucleus sampling, in (0, 1]: after --top-k, draw only from the most probable tokens whose "
+                   "probabilities add up to P (1: off; no effect on greedy decoding)")
     p.add_argument("--seed", type=int, default=1234, help="Seed of the sampler key")
     p.add_argument("--sampler-step", type=int, default=0,
                    help="Step of the stateless sampler (default 0); train.py's --sample-every samples use the "
@@ -87,6 +90,12 @@ def main(argv=None) -> int:
         return _fail(f"unknown --model-dtype {args.model_dtype!r}")
     if args.max_new_tokens < 1 or args.temperature < 0 or args.top_k < 0:
         return _fail("--max-new-tokens must be >= 1, --temperature and --top-k >= 0")
+    try:  # NaN and a value that rounds to 0 in float32 fail too
+        from .utils.sampling import check_top_p
+
+        check_top_p(args.top_p)
+    except ValueError:
+        return _fail(f"--top-p must be in (0, 1], got {args.top_p}")
     if args.num_samples < 1:
         return _fail("--num-samples must be >= 1")
     if args.prompt_ids_file and args.prompts_file is None:
@@ -176,11 +185,11 @@ def main(argv=None) -> int:
         if batched:
             rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                   key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
-                                  graph=args.decode_graph)
+                                  graph=args.decode_graph, top_p=args.top_p)
         else:
             ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                            key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
-                           graph=args.decode_graph)
+                           graph=args.decode_graph, top_p=args.top_p)
     except ValueError as e:
         return _fail(str(e))
     dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished

@@ -384,7 +384,7 @@ class DecodeGraph:
 
     @torch.no_grad()
     def begin(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
-              key: int = 0, step: int = 0) -> int:
+              key: int = 0, step: int = 0, top_p: float = 1.0) -> int:
         """Start a call: check the request, prefill every row (fewer prompts than ``batch`` are padded with
         copies of the first one: a row's tokens do not depend on the other rows), and write ``logits``,
         ``pos0`` and ``ctl`` (t = 0). Returns the number of prompts. Nothing is replayed."""
@@ -404,7 +404,7 @@ class DecodeGraph:
         self._wait_params()
         self.logits.copy_(logits)
         self.pos0.copy_(self.cache.pos0)
-        D.write_ctl(self.ctl, 0, temperature, top_k, key, step)
+        D.write_ctl(self.ctl, 0, temperature, top_k, key, step, top_p=top_p)
         self._t = 0  # the host's count of the passes of this call: ctl's t, which is never read back
         return len(rows)
 
@@ -420,10 +420,10 @@ class DecodeGraph:
 
     @torch.no_grad()
     def run(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
-            key: int = 0, step: int = 0, eos_id: Optional[int] = None) -> List[List[int]]:
+            key: int = 0, step: int = 0, eos_id: Optional[int] = None, top_p: float = 1.0) -> List[List[int]]:
         """What :func:`generate_batch` returns for these arguments."""
         n_new = int(max_new_tokens)
-        n_rows = self.begin(prompts, n_new, temperature, top_k, key, step)
+        n_rows = self.begin(prompts, n_new, temperature, top_k, key, step, top_p=top_p)
         seen = 0  # tokens of every row the host has looked at
         done = [False] * n_rows
         t = 0
@@ -462,7 +462,7 @@ MAX_BATCH = 64
 @torch.no_grad()
 def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0,
                    top_k: int = 0, key: int = 0, eos_id: Optional[int] = None, step: int = 0,
-                   graph: bool = False) -> List[List[int]]:
+                   graph: bool = False, top_p: float = 1.0) -> List[List[int]]:
     """:func:`generate` for B prompts at once: the ids generated after each of ``prompts``. New token
     ``t`` of every row comes from one ``D.sample(logits[B, V], ..., token_key(key, t), step)``, row
     ``b``'s draw being the sampler's row ``b``: row 0 equals ``generate`` with the same arguments, and
@@ -484,13 +484,13 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     flat = model.flat
     if graph and graph_supported(model):
         return DecodeGraph(model, B, max(len(p) for p in rows) + n_new).run(
-            rows, n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id)
+            rows, n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id, top_p=top_p)
     cache = BatchKVCache(a, B, max(len(p) for p in rows) + n_new, flat.device, flat.dtype)
     logits = _prefill_rows(model, rows, cache)
     out: List[List[int]] = [[] for _ in rows]
     live = [True] * B
     for t in range(n_new):
-        nxt = D.sample(logits, temperature, top_k, token_key(key, t), step)
+        nxt = D.sample(logits, temperature, top_k, token_key(key, t), step, top_p=top_p)
         for b, tok in enumerate(nxt.tolist()):
             if live[b]:
                 out[b].append(tok)
@@ -503,10 +503,11 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
 
 @torch.no_grad()
 def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
-             key: int = 0, eos_id: Optional[int] = None, step: int = 0, graph: bool = False) -> List[int]:
+             key: int = 0, eos_id: Optional[int] = None, step: int = 0, graph: bool = False,
+             top_p: float = 1.0) -> List[int]:
     """The ids generated after ``prompt_ids`` (at most ``max_new_tokens``; ends after ``eos_id``,
-    which is included). ``temperature == 0`` is greedy; otherwise temperature / top-k sampling with
-    the stateless sampler under ``(key, step)``. ``graph=True`` decodes with a one-row
+    which is included). ``temperature == 0`` is greedy; otherwise temperature / top-k / top-p sampling
+    (``top_p`` in (0, 1], 1: off) with the stateless sampler under ``(key, step)``. ``graph=True`` decodes with a one-row
     :class:`DecodeGraph` (the multi-row kernels at B = 1 return the one-row kernels' bits)."""
     prompt = [int(t) for t in prompt_ids]
     n_new = int(max_new_tokens)
@@ -524,12 +525,13 @@ def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature:
     flat = model.flat
     if graph and graph_supported(model):
         return DecodeGraph(model, 1, len(prompt) + n_new).run(
-            [prompt], n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id)[0]
+            [prompt], n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id,
+            top_p=top_p)[0]
     cache = KVCache(a, len(prompt) + n_new, flat.device, flat.dtype)
     logits = prefill(model, prompt, cache)
     out: List[int] = []
     for t in range(n_new):
-        nxt = D.sample(logits, temperature, top_k, token_key(key, t), step)
+        nxt = D.sample(logits, temperature, top_k, token_key(key, t), step, top_p=top_p)
         out.append(int(nxt[0]))
         if (eos_id is not None and out[-1] == eos_id) or t == n_new - 1:
             break

@@ -121,17 +121,28 @@ def attn_rows(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos
     return torch.stack([attn(q[b], k_cache[b], v_cache[b], int(p) + int(t) + 1) for b, p in enumerate(positions)])
 
 
-def sample(logits: torch.Tensor, temperature: float, top_k: int, key: int, step: int) -> torch.Tensor:
+def _check_top_p(top_p: float) -> float:
+    """``top_p`` unchanged, after the definition's check (the kernel takes it as float32: a value that
+    rounds to 0 there is as wrong as 0)."""
+    from ..utils.sampling import check_top_p
+
+    check_top_p(top_p)
+    return float(top_p)
+
+
+def sample(logits: torch.Tensor, temperature: float, top_k: int, key: int, step: int,
+           top_p: float = 1.0) -> torch.Tensor:
     """One token per row of ``logits`` ([V] or [R, V]): int64 tensor [R] on ``logits``' device.
     The definition is ``utils.sampling.sample_reference``."""
+    top_p = _check_top_p(top_p)
     x2 = logits.reshape(-1, logits.shape[-1])
     if native(x2) and x2.shape[1] % 8 == 0:
         out = torch.empty(x2.shape[0], dtype=torch.int64, device=x2.device)
-        kernels().sample_(x2.contiguous(), out, float(temperature), int(top_k), int(key), int(step))
+        kernels().sample_(x2.contiguous(), out, float(temperature), int(top_k), int(key), int(step), top_p)
         return out
     from ..utils.sampling import sample_reference
 
-    return sample_reference(x2, temperature, top_k, key, step).to(x2.device)
+    return sample_reference(x2, temperature, top_k, key, step, top_p=top_p).to(x2.device)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -140,7 +151,7 @@ def sample(logits: torch.Tensor, temperature: float, top_k: int, key: int, step:
 # kernel route never reads it back. The composed route (CPU, fp64) reads it on the host and calls the
 # definitions above.
 # ---------------------------------------------------------------------------------------------
-CTL_T, CTL_KEY_LO, CTL_KEY_HI, CTL_STEP, CTL_TEMPERATURE, CTL_TOP_K = range(6)
+CTL_T, CTL_KEY_LO, CTL_KEY_HI, CTL_STEP, CTL_TEMPERATURE, CTL_TOP_K, CTL_TOP_P = range(7)
 CTL_WORDS = 8
 _M32 = 0xFFFFFFFF
 
@@ -149,14 +160,18 @@ def new_ctl(device) -> torch.Tensor:
     return torch.zeros(CTL_WORDS, dtype=torch.int32, device=device)
 
 
-def write_ctl(ctl: torch.Tensor, t: int, temperature: float, top_k: int, key: int, step: int) -> None:
+def write_ctl(ctl: torch.Tensor, t: int, temperature: float, top_k: int, key: int, step: int,
+              top_p: float = 1.0) -> None:
     """Fill the control block: step counter ``t``, and the sampling arguments of ``sample`` -- the
-    temperature as the float32 the kernel takes, the call's key (not a token's) as two words."""
+    temperature as the float32 the kernel takes, the call's key (not a token's) as two words, and
+    ``top_p`` as float32 bits, 0 standing for 1.0 (off)."""
+    top_p = _check_top_p(top_p)
     if not (0.0 <= float(temperature) < math.inf) or int(top_k) < 0 or int(t) < 0:
         raise ValueError("temperature must be finite and >= 0, top_k and t >= 0")
     tbits = struct.unpack("<I", struct.pack("<f", float(temperature)))[0]
+    pbits = 0 if top_p == 1.0 else struct.unpack("<I", struct.pack("<f", top_p))[0]
     words = [int(t) & _M32, int(key) & _M32, (int(key) >> 32) & _M32, int(step) & _M32, tbits,
-             min(int(top_k), 0x7FFFFFFF), 0, 0]
+             min(int(top_k), 0x7FFFFFFF), pbits, 0]
     ctl.copy_(torch.tensor(struct.unpack("<8i", struct.pack("<8I", *words)), dtype=torch.int32))
 
 
@@ -166,6 +181,14 @@ def read_ctl(ctl: torch.Tensor) -> Tuple[int, float, int, int, int]:
     t = w[CTL_T] - (1 << 32) if w[CTL_T] >> 31 else w[CTL_T]
     temperature = struct.unpack("<f", struct.pack("<I", w[CTL_TEMPERATURE]))[0]
     return t, temperature, w[CTL_TOP_K], w[CTL_KEY_LO] | (w[CTL_KEY_HI] << 32), w[CTL_STEP]
+
+
+def read_ctl_top_p(ctl: torch.Tensor) -> float:
+    """``top_p`` of a control block, as the kernel reads it: the float32 in word CTL_TOP_P, and 1.0 (off)
+    for a word of 0 or a value that is not inside (0, 1)."""
+    w = int(ctl[CTL_TOP_P]) & _M32
+    p = struct.unpack("<f", struct.pack("<I", w))[0]
+    return p if 0.0 < p < 1.0 else 1.0
 
 
 def ctl_advance_(ctl: torch.Tensor) -> None:
@@ -213,7 +236,7 @@ def attn_part(batch: int, hq: int, smax: int, d: int, device) -> torch.Tensor:
 
 
 def sample_dev_(logits: torch.Tensor, ctl: torch.Tensor, tok: torch.Tensor, out: torch.Tensor) -> None:
-    """``sample(logits, temperature, top_k, token_key(key, t), step)`` with all five taken from ``ctl``:
+    """``sample(logits, temperature, top_k, token_key(key, t), step, top_p)`` with all six taken from ``ctl``:
     row b's token goes to ``tok[b]`` (int64, B elements) and to ``out[b, t]`` (int64 ``[B, n_cap]``)."""
     if native(logits) and logits.dim() == 2 and logits.shape[1] % 8 == 0:
         kernels().sample_dev_(logits, ctl, tok, out)
@@ -221,7 +244,7 @@ def sample_dev_(logits: torch.Tensor, ctl: torch.Tensor, tok: torch.Tensor, out:
     from ..utils.sampling import token_key
 
     t, temperature, top_k, key, step = read_ctl(ctl)
-    nxt = sample(logits, temperature, top_k, token_key(key, t), step).to(tok.device)
+    nxt = sample(logits, temperature, top_k, token_key(key, t), step, read_ctl_top_p(ctl)).to(tok.device)
     tok.copy_(nxt.view_as(tok))
     if 0 <= t < out.shape[1]:
         out[:, t] = nxt

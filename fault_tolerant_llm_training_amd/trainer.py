@@ -732,6 +732,7 @@ def train(args) -> int:
 
     sample_every = int(getattr(args, "sample_every", 0) or 0)
     sample_count = int(getattr(args, "sample_count", 1) or 1)
+    sample_top_p = float(getattr(args, "sample_top_p", 1.0))
     sample_prompt, sample_tok = None, None
     if sample_every > 0:
         from . import generation
@@ -757,9 +758,11 @@ def train(args) -> int:
                             "a multiple of 8; the samples are decoded eagerly")
         if sample_count > 1:
             logger.info(f"Sampling: {sample_count} samples per boundary, decoded as one batch")
+        sample_top_p_clause = f", top-p {sample_top_p:g}" if sample_top_p != 1.0 else ""
         logger.info(f"Sampling: every {sample_every} steps and after the last step -- rank 0 generates "
                     f"{args.sample_tokens} tokens from a prompt of {len(sample_prompt)} (temperature "
-                    f"{args.sample_temperature:g}, top-k {args.sample_top_k}; key {sample_key:#018x} from --seed, "
+                    f"{args.sample_temperature:g}, top-k {args.sample_top_k}{sample_top_p_clause}; key "
+                    f"{sample_key:#018x} from --seed, "
                     "sampler step = training step); the other ranks wait in the next vote (keep it far below "
                     "--peer-timeout)" + ("; --sample-ema: decoded from the parameter EMA" if sample_ema else ""))
 
@@ -770,6 +773,8 @@ def train(args) -> int:
         nonlocal sample_graph
         kw = dict(temperature=args.sample_temperature, top_k=args.sample_top_k, key=sample_key, step=step_now,
                   eos_id=getattr(sample_tok, "eos_token_id", None))
+        if sample_top_p != 1.0:  # --sample-top-p
+            kw["top_p"] = sample_top_p
         if getattr(args, "sample_graph", False) and generation.graph_supported(model):
             first = sample_graph is None
             if first:  # here, not at start-up: the flat buffers' addresses are final

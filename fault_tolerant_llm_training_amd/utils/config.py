@@ -335,6 +335,13 @@ def build_parser() -> argparse.ArgumentParser:
     )
     parser.add_argument("--sample-top-k", type=int, default=0, help="Top-k of --sample-every (0: all tokens)")
     parser.add_argument(
+        "--sample-top-p",
+        type=float,
+        default=1.0,
+        help="Top-p (nucleus) of --sample-every, in (0, 1]: after top-k, only the most probable tokens whose "
+        "probabilities add up to P are drawn from (1: off). No effect on greedy samples",
+    )
+    parser.add_argument(
         "--sample-count",
         type=int,
         default=1,
@@ -433,6 +440,12 @@ def get_args(argv=None) -> argparse.Namespace:
         parser.error(f"--sample-count must be in 1 .. 16, got {args.sample_count}")
     if args.sample_count > 1 and args.sample_every == 0:
         parser.error("--sample-count needs --sample-every")
+    try:  # NaN and a value that rounds to 0 in float32 fail too
+        from .sampling import check_top_p
+
+        check_top_p(args.sample_top_p)
+    except ValueError:
+        parser.error(f"--sample-top-p must be in (0, 1], got {args.sample_top_p}")
     if args.sample_graph and args.sample_every == 0:
         parser.error("--sample-graph needs --sample-every")
     if args.sample_every > 0:
