@@ -40,14 +40,16 @@ void pread_all(int fd, uint8_t* p, uint64_t len, uint64_t off) {
   }
 }
 
-// O_DIRECT read of an aligned body; false if the kernel refuses it (EINVAL) before any byte.
+// O_DIRECT read of an aligned body; false if the kernel refuses it before any byte: EINVAL, or
+// EFAULT where it cannot pin the destination pages for DMA (in a virtual machine pinned host
+// memory can be a device mapping, which a buffered read still copies into).
 bool pread_direct(int dfd, uint8_t* p, uint64_t len, uint64_t off) {
   uint64_t done = 0;
   while (done < len) {
     const ssize_t n = ::pread(dfd, p + done, std::min<uint64_t>(len - done, 1ull << 30), (off_t)(off + done));
     if (n < 0) {
       if (errno == EINTR) continue;
-      if (errno == EINVAL && done == 0) return false;
+      if ((errno == EINVAL || errno == EFAULT) && done == 0) return false;
       throw std::runtime_error(std::string("pread(O_DIRECT): ") + strerror(errno));
     }
     if (n == 0) throw std::runtime_error("pread(O_DIRECT): unexpected end of file");

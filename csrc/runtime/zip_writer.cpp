@@ -54,14 +54,17 @@ void pwrite_all(int fd, const void* p, uint64_t n, uint64_t off) {
   }
 }
 
-// O_DIRECT write of an aligned body; false if the kernel/filesystem rejects it.
+// O_DIRECT write of an aligned body; false if the kernel/filesystem rejects it: EINVAL, or
+// EFAULT where the kernel cannot pin the source pages for DMA (in a virtual machine
+// hipHostMalloc memory can be a device mapping, which a buffered write still copies from).
+// The caller then writes the whole body buffered, which reports a truly bad address itself.
 bool pwrite_direct(int fd, const uint8_t* p, uint64_t n, uint64_t off) {
   while (n > 0) {
     const uint64_t k = n > (1ull << 30) ? (1ull << 30) : n;
     ssize_t w = ::pwrite(fd, p, k, (off_t)off);
     if (w < 0) {
       if (errno == EINTR) continue;
-      if (errno == EINVAL) return false;
+      if (errno == EINVAL || errno == EFAULT) return false;
       throw std::runtime_error(std::string("pwrite(O_DIRECT) failed: ") + strerror(errno));
     }
     if ((uint64_t)w % DIRECT_ALIGN) throw std::runtime_error("short unaligned O_DIRECT write");

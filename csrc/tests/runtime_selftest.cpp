@@ -63,11 +63,25 @@ void test_signals() {
   const std::vector<int> sigs = {SIGUSR1, SIGTERM, SIGUSR2, SIGHUP};
   signals_install(sigs);
   // deliveries from several threads race with the main thread's polling (distinct
-  // signals: standard signals of one number coalesce while pending)
+  // signals: standard signals of one number coalesce while pending). The kernel may hand a
+  // process-directed signal to any thread that has it unblocked, a sender included, and
+  // ThreadSanitizer drops one that lands on a thread it has not set up yet or has already
+  // torn down. So a sender is created with the signals blocked, unblocks them once it runs,
+  // and stays until every handler has run.
+  auto await_all = [] {
+    for (int spin = 0; spin < 2000 && signals_count() < 4; ++spin) usleep(500);
+  };
+  signals_block(sigs, true);
   std::vector<std::thread> senders;
-  for (int s : sigs) senders.emplace_back([s] { kill(getpid(), s); });
+  for (int s : sigs)
+    senders.emplace_back([s, &sigs, &await_all] {
+      signals_block(sigs, false);
+      kill(getpid(), s);
+      await_all();
+    });
+  signals_block(sigs, false);
+  await_all();
   for (auto& th : senders) th.join();
-  for (int spin = 0; spin < 2000 && signals_count() < 4; ++spin) usleep(500);
   CHECK(signals_count() == 4, "signal count %llu", (unsigned long long)signals_count());
   const int first = signals_pending();
   CHECK(first == SIGUSR1 || first == SIGTERM || first == SIGUSR2 || first == SIGHUP, "first signal %d", first);
