@@ -114,6 +114,19 @@ def _needs(obj: Path, src: Path, headers) -> bool:
 W4_CHECKED = ("gemm_w4_fwd", "gemm_w4_dx", "gemm_w4_dw")
 
 
+# Translation units compiled without the packed fp32 instructions (v_pk_fma_f32, v_pk_mul_f32,
+# v_pk_add_f32). The results are the same either way (the packed forms round each element as the
+# scalar ones do); the reason is registers. With them the compiler pairs the accumulators of the
+# decode_w8 kernels across activation rows (about 2270 v_pk_fma_f32) and the pairing costs VGPRs:
+# 74 -> 114 for the one-row gemv, 127 -> 242 for the 8-row tile, and the 4-row SwiGLU tile reaches
+# 256 with spills to scratch. Without them every kernel of the unit stays at or under 128 VGPRs with
+# no scratch, which the 512-thread workgroups of the multi-row forms need to fit twice per CU. The
+# two builds were compared by their register counts only, not timed against each other. The other
+# units keep the flags they were tuned with.
+NO_PACKED_FP32 = ("decode_w8",)
+NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+
+
 def _asm_of(src: Path, obj: Path) -> Path:
     return obj.parent / f"{src.stem}-hip-amdgcn-amd-amdhsa-{ARCH}.s"
 
@@ -124,6 +137,8 @@ def _compile(src: Path, obj: Path, flags, device: bool):
         cmd += [f"--offload-arch={ARCH}", "-x", "hip"]
         if src.stem in W4_CHECKED:
             cmd += ["-save-temps=obj"]
+        if src.stem in NO_PACKED_FP32:
+            cmd += NO_PACKED_FP32_FLAGS
     cmd += ["-c", str(src), "-o", str(obj)]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(obj.parent))
     if r.returncode != 0:

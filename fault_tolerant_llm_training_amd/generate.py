@@ -18,6 +18,11 @@ average, rounded to nearest in ``--model-dtype``.
 
 ``--decode-graph`` decodes with ``generation.DecodeGraph``: one captured HIP graph per token, replayed,
 instead of about nine launches per layer issued from Python. The ids are the same.
+
+``--weight-dtype fp8`` decodes from weight-only FP8 copies of the projection, FFN and head weights
+(``generation.Fp8Weights``: e4m3 codes, one fp32 scale per output row), built once after the checkpoint
+(or its ``ema`` entry) is loaded; one line on stderr gives the quantize time and the bytes. The prompt is
+still prefilled with the model's own weights.
 """
 from __future__ import annotations
 
@@ -66,6 +71,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--use-ema", action="store_true",
                    help="Generate from the file's `ema` entry (the parameter average of a --ema-decay run), rounded "
                    "to nearest in --model-dtype, instead of `model`; an error if the file has none")
+    p.add_argument("--weight-dtype", type=str, default="model", choices=["model", "fp8"],
+                   help="Weights the decode steps read: `model` (the checkpoint's, in --model-dtype) or `fp8` "
+                   "(weight-only e4m3 with one scale per output row, quantized once after loading: half the bytes "
+                   "per token; bf16 / fp16 models on the GPU, any dtype but fp32 on --device cpu)")
     p.add_argument("--json", action="store_true", help="Print one JSON line instead of the text")
     return p
 
@@ -98,6 +107,10 @@ def main(argv=None) -> int:
         return _fail(f"--top-p must be in (0, 1], got {args.top_p}")
     if args.num_samples < 1:
         return _fail("--num-samples must be >= 1")
+    if args.weight_dtype == "fp8" and (args.model_dtype == "fp32" or (args.device == "cuda"
+                                                                       and args.model_dtype not in ("bf16", "fp16"))):
+        return _fail(f"--weight-dtype fp8 needs --model-dtype bf16 or fp16 on the GPU (on --device cpu: any but fp32), "
+                     f"got {args.model_dtype} on {args.device}")
     if args.prompt_ids_file and args.prompts_file is None:
         return _fail("--prompt-ids-file needs --prompts-file")
     lines = None
@@ -178,6 +191,19 @@ def main(argv=None) -> int:
     del ckpt
     model.eval()
     eos = getattr(tok, "eos_token_id", None) if tok is not None else None
+    weights = None
+    if args.weight_dtype == "fp8":
+        from .generation import Fp8Weights
+
+        tq = time.perf_counter()
+        try:
+            weights = Fp8Weights(model)
+        except ValueError as e:
+            return _fail(str(e))
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+        print(f"generate: fp8 weights: {weights.nbytes / 2 ** 20:.1f} MiB of codes and scales, quantized in "
+              f"{time.perf_counter() - tq:.3f} s", file=sys.stderr, flush=True)
     if device.type == "cuda":
         torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -185,11 +211,11 @@ def main(argv=None) -> int:
         if batched:
             rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                   key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
-                                  graph=args.decode_graph, top_p=args.top_p)
+                                  graph=args.decode_graph, top_p=args.top_p, weights=weights)
         else:
             ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                            key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
-                           graph=args.decode_graph, top_p=args.top_p)
+                           graph=args.decode_graph, top_p=args.top_p, weights=weights)
     except ValueError as e:
         return _fail(str(e))
     dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished

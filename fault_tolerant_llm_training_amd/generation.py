@@ -36,6 +36,14 @@ the sampling arguments, which the device-step ops of ``ops/decode.py`` read and 
 launch advances. The attention grid covers the cache's capacity, not the current key count, so the
 captured launches are right for any token of any call that fits the capacity; the results are those
 of the eager loop bit for bit.
+
+Weight-only FP8 (:class:`Fp8Weights`, the ``weights`` argument of the decode functions): decoding is
+bound by the weight bytes, so the five products of a pass can read e4m3 codes with one fp32 scale per
+output row (``utils/fp8.py``) instead of the model's weights -- every ``gemv*`` call becomes its ``_w8``
+form on the same activations (``csrc/kernels/decode_w8.hip``) and nothing else changes. Prefill keeps
+the training forward kernels on the model's own weights (it is bound by compute, and it is the code the
+trainer runs), so the prompt's K/V and the logits after the prompt come from the unquantized weights.
+With ``weights=None`` every path returns the bits it returned before.
 """
 from __future__ import annotations
 
@@ -140,7 +148,85 @@ class BatchKVCache:
         return self._pos0
 
 
-def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor]) -> torch.Tensor:
+class Fp8Weights:
+    """The decode weights of ``model`` in weight-only FP8: e4m3 codes (uint8) and one fp32 scale per
+    output row (``utils/fp8.py``) of ``wqkv``, ``wo``, ``[w1; w3]`` and ``w2`` of every layer and of the
+    LM head, quantized once here (after a wait at the parameter gate) by ``D.quantize_rows``. Embedding
+    and norm weights are not touched: the decode functions keep reading them from the model.
+
+    ``layers[i]`` is ``(wqkv, wo, w13, w2)`` and ``head`` the LM head, each a ``(codes, scale)`` pair.
+    The buffers are a copy: after the parameters change, :meth:`requantize` refreshes them in place
+    (same tensors, so a :class:`DecodeGraph` captured on them stays valid).
+
+    Refused: fp32 models (no FP8 kernel takes fp32 activations), fp64 models on the GPU (they decode by
+    the composed definitions, which would silently stand in for a kernel), and any weight whose K is
+    not a multiple of 16 (the codes move in 16-byte vectors)."""
+
+    def __init__(self, model):
+        flat = model.flat
+        if flat.dtype == torch.float32 or (flat.device.type == "cuda"
+                                           and flat.dtype not in (torch.bfloat16, torch.float16)):
+            raise ValueError(f"Fp8Weights needs a bf16 or fp16 model on the GPU (on the CPU: any dtype but fp32), "
+                             f"got {flat.device.type} / {flat.dtype}")
+        self.model = model
+        for name, w in self._sources():
+            if w.dim() != 2 or w.shape[1] % 16 != 0:
+                raise ValueError(f"Fp8Weights: {name} has shape {tuple(w.shape)}; K must be a multiple of 16 "
+                                 "(16-byte vectors of e4m3 codes)")
+        self.layers: List[tuple] = []
+        self.head: Optional[tuple] = None
+        self.requantize()
+
+    def _sources(self):
+        for i, layer in enumerate(self.model.layers.values()):
+            at, ff = layer.attention, layer.feed_forward
+            yield f"layers.{i}.wqkv", at.wqkv
+            yield f"layers.{i}.wo", at.wo.weight
+            yield f"layers.{i}.w13", ff.w13
+            yield f"layers.{i}.w2", ff.w2.weight
+        yield "output", self.model.output.weight
+
+    @torch.no_grad()
+    def requantize(self) -> None:
+        """Quantize the model's current parameters into the buffers (allocated on the first call)."""
+        emb_r, layer_r, final_r = self.model._ranges
+        for r in (emb_r, *layer_r, final_r):
+            self.model._wait(r)
+        old = [q for layer in self.layers for q in layer] + ([self.head] if self.head is not None else [])
+        new = [D.quantize_rows(w, old[j] if old else None) for j, (_, w) in enumerate(self._sources())]
+        self.layers = [tuple(new[4 * i : 4 * i + 4]) for i in range(len(new) // 4)]
+        self.head = new[-1]
+
+    @property
+    def nbytes(self) -> int:
+        return sum(c.numel() * c.element_size() + s.numel() * s.element_size()
+                   for layer in (*self.layers, (self.head,)) for c, s in layer)
+
+
+# One product of a pass: the model's weight, or its FP8 pair ``q`` (``(codes, scale)``) where given.
+def _mv(x, w, q):
+    return D.gemv(x, w) if q is None else D.gemv_w8(x, q[0], q[1])
+
+
+def _mv_swiglu(x, w13, q):
+    return D.gemv_swiglu(x, w13) if q is None else D.gemv_swiglu_w8(x, q[0], q[1])
+
+
+def _mv_rows(x, w, q):
+    return D.gemv_rows(x, w) if q is None else D.gemv_rows_w8(x, q[0], q[1])
+
+
+def _mv_swiglu_rows(x, w13, q):
+    return D.gemv_swiglu_rows(x, w13) if q is None else D.gemv_swiglu_rows_w8(x, q[0], q[1])
+
+
+def _check_weights(model, weights: Optional[Fp8Weights]) -> None:
+    if weights is not None and weights.model is not model:
+        raise ValueError("these Fp8Weights were quantized from another model")
+
+
+def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor],
+                  weights: Optional[Fp8Weights] = None) -> torch.Tensor:
     """Final norm and LM head on one row: h, d [1, dim] -> logits [V]."""
     a = model.model_args
     ln = a.norm_type == "layernorm"
@@ -149,7 +235,7 @@ def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor]) -> torch.Te
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return D.gemv(hn.reshape(-1), model.output.weight)
+    return _mv(hn.reshape(-1), model.output.weight, None if weights is None else weights.head)
 
 
 @torch.no_grad()
@@ -191,8 +277,11 @@ def prefill(model, tokens: Union[Sequence[int], torch.Tensor], cache: KVCache) -
 
 
 @torch.no_grad()
-def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache) -> torch.Tensor:
-    """Append one token at position ``cache.length``; returns the logits [V] after it."""
+def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache,
+                weights: Optional[Fp8Weights] = None) -> torch.Tensor:
+    """Append one token at position ``cache.length``; returns the logits [V] after it. ``weights``: the
+    five products read these FP8 weights instead of the model's."""
+    _check_weights(model, weights)
     pos = cache.length
     if pos >= cache.max_len:
         raise ValueError(f"the cache is full ({cache.max_len} tokens)")
@@ -209,26 +298,28 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache) -> torch
     for i, layer in enumerate(model.layers.values()):
         model._wait(layer_r[i])
         at, ff = layer.attention, layer.feed_forward
+        qqkv, qo, q13, q2 = (None,) * 4 if weights is None else weights.layers[i]
         if d is None:
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = D.gemv(xn.reshape(-1), at.wqkv)
+        qkv = _mv(xn.reshape(-1), at.wqkv, qqkv)
         D.qkv_append_(qkv, cos, sin, pos, cache.k[i], cache.v[i])
         o = D.attn(qkv[: hq * hd], cache.k[i], cache.v[i], pos + 1)
-        da = D.gemv(o, at.wo.weight)
+        da = _mv(o, at.wo.weight, qo)
         h, hn = Fx.add_norm(h, da.view(1, -1), layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = D.gemv(D.gemv_swiglu(hn.reshape(-1), ff.w13), ff.w2.weight).view(1, -1)
+        d = _mv(_mv_swiglu(hn.reshape(-1), ff.w13, q13), ff.w2.weight, q2).view(1, -1)
     cache.length = pos + 1
-    return _final_logits(model, h, d)
+    return _final_logits(model, h, d, weights)
 
 
-def _rows_pass(model, tok: torch.Tensor, append, attend, wait) -> torch.Tensor:
+def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional[Fp8Weights] = None) -> torch.Tensor:
     """One pass over the weights for the B rows of ``tok`` [B, 1]: embedding, the layers, final norm and
     head; returns the logits [B, V]. The two ops that touch the cache are the caller's: ``append(i, qkv)``
     rotates Q in place and stores layer i's K and V, ``attend(i, q)`` returns its attention output
     [B, Hq D]. ``wait(range)`` is the parameter-gate wait before each range of weights (None: the caller
-    has waited for all of them). :func:`decode_step_rows` and :class:`DecodeGraph` share this loop."""
+    has waited for all of them). ``weights``: the products read these FP8 weights instead of the model's.
+    :func:`decode_step_rows` and :class:`DecodeGraph` share this loop."""
     a = model.model_args
     ln = a.norm_type == "layernorm"
     hq, hd = a.n_heads, a.head_dim
@@ -241,29 +332,32 @@ def _rows_pass(model, tok: torch.Tensor, append, attend, wait) -> torch.Tensor:
         if wait is not None:
             wait(layer_r[i])
         at, ff = layer.attention, layer.feed_forward
+        qqkv, qo, q13, q2 = (None,) * 4 if weights is None else weights.layers[i]
         if d is None:
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = D.gemv_rows(xn, at.wqkv)
+        qkv = _mv_rows(xn, at.wqkv, qqkv)
         append(i, qkv)
         o = attend(i, qkv[:, : hq * hd])
-        da = D.gemv_rows(o, at.wo.weight)
+        da = _mv_rows(o, at.wo.weight, qo)
         h, hn = Fx.add_norm(h, da, layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = D.gemv_rows(D.gemv_swiglu_rows(hn, ff.w13), ff.w2.weight)
+        d = _mv_rows(_mv_swiglu_rows(hn, ff.w13, q13), ff.w2.weight, q2)
     if wait is not None:
         wait(final_r)
     if d is None:
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return D.gemv_rows(hn, model.output.weight)
+    return _mv_rows(hn, model.output.weight, None if weights is None else weights.head)
 
 
 @torch.no_grad()
-def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: BatchKVCache, t: int) -> torch.Tensor:
+def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: BatchKVCache, t: int,
+                     weights: Optional[Fp8Weights] = None) -> torch.Tensor:
     """Decode step ``t`` (0, 1, ...) of a batch: append ``tokens[b]`` at position ``pos0[b] + t`` of
     row ``b``; returns the logits [B, V] after them. The loop of :func:`decode_step` on B rows."""
+    _check_weights(model, weights)
     B, t = cache.batch, int(t)
     if t != cache.steps:
         raise ValueError(f"decode step {t} out of order (the cache has taken {cache.steps})")
@@ -278,7 +372,7 @@ def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: B
     logits = _rows_pass(
         model, tok,
         lambda i, qkv: D.qkv_append_rows_(qkv, cos, sin, pos0, t, cache.k[i], cache.v[i], lengths),
-        lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait)
+        lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait, weights)
     cache.steps = t + 1
     return logits
 
@@ -317,18 +411,22 @@ class DecodeGraph:
     ``logits``, then ``t += 1``: a single chain of launches on one stream.
 
     The capture happens here, once (``captures`` counts them), so build the object when the parameters'
-    addresses are final. :meth:`run` serves any request of up to ``batch`` rows that fits ``max_len``."""
+    addresses are final. :meth:`run` serves any request of up to ``batch`` rows that fits ``max_len``.
+    With ``weights`` (:class:`Fp8Weights`) the captured products are the ``_w8`` ops on its buffers; the
+    prefill of every call still runs on the model's own weights."""
 
     EOS_CHECK_EVERY = 16  # tokens between two looks at the generated ids (one copy to the host each)
 
-    def __init__(self, model, batch: int, max_len: int):
+    def __init__(self, model, batch: int, max_len: int, weights: Optional[Fp8Weights] = None):
         flat, a = model.flat, model.model_args
+        _check_weights(model, weights)
         if not graph_supported(model):  # before anything is allocated or a capture opens
             raise ValueError("DecodeGraph needs a GPU model of a kernel dtype (bf16, fp16 or fp32) whose vocabulary "
                              f"is a multiple of 8 (the device sampler's rows), got {flat.device.type} / {flat.dtype} "
                              f"/ vocabulary {a.vocab_size}")
         dev = flat.device
         self.model = model
+        self.weights = weights
         self.cache = BatchKVCache(a, batch, max_len, dev, flat.dtype)
         self.batch, self.max_len = self.cache.batch, self.cache.max_len
         B = self.batch
@@ -360,7 +458,8 @@ class DecodeGraph:
         logits = _rows_pass(
             model, self.tok,
             lambda i, qkv: D.qkv_append_rows_dev_(qkv, cos, sin, pos0, ctl, cache.k[i], cache.v[i]),
-            lambda i, q: D.attn_rows_dev(q, cache.k[i], cache.v[i], pos0, ctl, self.part, self.o), None)
+            lambda i, q: D.attn_rows_dev(q, cache.k[i], cache.v[i], pos0, ctl, self.part, self.o), None,
+            self.weights)
         self.logits.copy_(logits)
         D.ctl_advance_(ctl)
 
@@ -462,7 +561,8 @@ MAX_BATCH = 64
 @torch.no_grad()
 def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0,
                    top_k: int = 0, key: int = 0, eos_id: Optional[int] = None, step: int = 0,
-                   graph: bool = False, top_p: float = 1.0) -> List[List[int]]:
+                   graph: bool = False, top_p: float = 1.0,
+                   weights: Optional[Fp8Weights] = None) -> List[List[int]]:
     """:func:`generate` for B prompts at once: the ids generated after each of ``prompts``. New token
     ``t`` of every row comes from one ``D.sample(logits[B, V], ..., token_key(key, t), step)``, row
     ``b``'s draw being the sampler's row ``b``: row 0 equals ``generate`` with the same arguments, and
@@ -470,7 +570,9 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     included) and keeps its batch slot -- its further tokens are computed and dropped, so no other
     row's draw or position shifts. Identical prompts are prefilled once. ``graph=True`` decodes with a
     :class:`DecodeGraph` built for this request (the same ids; keep the object yourself to reuse its
-    capture)."""
+    capture). ``weights``: decode with these FP8 weights (the prompts' K/V and the first token's logits
+    come from the prefill, on the unquantized weights)."""
+    _check_weights(model, weights)
     rows = [[int(t) for t in p] for p in prompts]
     n_new = int(max_new_tokens)
     a = model.model_args
@@ -483,7 +585,7 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
         return [[] for _ in rows]
     flat = model.flat
     if graph and graph_supported(model):
-        return DecodeGraph(model, B, max(len(p) for p in rows) + n_new).run(
+        return DecodeGraph(model, B, max(len(p) for p in rows) + n_new, weights).run(
             rows, n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id, top_p=top_p)
     cache = BatchKVCache(a, B, max(len(p) for p in rows) + n_new, flat.device, flat.dtype)
     logits = _prefill_rows(model, rows, cache)
@@ -497,18 +599,21 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
                 live[b] = eos_id is None or tok != eos_id
         if not any(live) or t == n_new - 1:
             break
-        logits = decode_step_rows(model, nxt, cache, t)
+        logits = decode_step_rows(model, nxt, cache, t, weights)
     return out
 
 
 @torch.no_grad()
 def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              key: int = 0, eos_id: Optional[int] = None, step: int = 0, graph: bool = False,
-             top_p: float = 1.0) -> List[int]:
+             top_p: float = 1.0, weights: Optional[Fp8Weights] = None) -> List[int]:
     """The ids generated after ``prompt_ids`` (at most ``max_new_tokens``; ends after ``eos_id``,
     which is included). ``temperature == 0`` is greedy; otherwise temperature / top-k / top-p sampling
     (``top_p`` in (0, 1], 1: off) with the stateless sampler under ``(key, step)``. ``graph=True`` decodes with a one-row
-    :class:`DecodeGraph` (the multi-row kernels at B = 1 return the one-row kernels' bits)."""
+    :class:`DecodeGraph` (the multi-row kernels at B = 1 return the one-row kernels' bits). ``weights``:
+    decode with these FP8 weights (:class:`Fp8Weights`); the prompt's K/V and the first token's logits
+    come from the prefill, on the unquantized weights."""
+    _check_weights(model, weights)
     prompt = [int(t) for t in prompt_ids]
     n_new = int(max_new_tokens)
     a = model.model_args
@@ -524,7 +629,7 @@ def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature:
         return []
     flat = model.flat
     if graph and graph_supported(model):
-        return DecodeGraph(model, 1, len(prompt) + n_new).run(
+        return DecodeGraph(model, 1, len(prompt) + n_new, weights).run(
             [prompt], n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id,
             top_p=top_p)[0]
     cache = KVCache(a, len(prompt) + n_new, flat.device, flat.dtype)
@@ -535,5 +640,5 @@ def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature:
         out.append(int(nxt[0]))
         if (eos_id is not None and out[-1] == eos_id) or t == n_new - 1:
             break
-        logits = decode_step(model, nxt, cache)
+        logits = decode_step(model, nxt, cache, weights)
     return out

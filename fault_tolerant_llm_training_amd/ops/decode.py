@@ -101,6 +101,71 @@ def gemv_swiglu_rows(x: torch.Tensor, w13: torch.Tensor) -> torch.Tensor:
     return torch.stack([gemv_swiglu(x[r], w13) for r in range(x.shape[0])])
 
 
+# ---------------------------------------------------------------------------------------------
+# The weight-only FP8 forms (csrc/kernels/decode_w8.hip): the weight is e4m3 codes (uint8 [N, K]) with
+# one fp32 scale per row, as ``utils.fp8`` defines them. GPU tensors of a 16-bit kernel dtype run the
+# kernels; CPU tensors and fp64 take the composed definition: the codes' values in x's dtype, ``mv``,
+# times ``scale``. Unlike ``gemv`` (``_gemv_ok``), the route is chosen by device and dtype alone: a GPU
+# operand the kernels cannot take (not contiguous, not 16-byte aligned, K % 16 != 0) is an error from
+# the op's host checks, not a detour through the composed route, whose float64 table lookup would be a
+# quiet and very slow stand-in for a kernel.
+# ---------------------------------------------------------------------------------------------
+def _w8_native(x: torch.Tensor, codes: torch.Tensor) -> bool:
+    return codes.is_cuda and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16)
+
+
+def quantize_rows(w: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """``(codes, scale)`` of ``w [N, K]`` (``utils.fp8.quantize_rows``); with ``out`` given, written into
+    that pair in place."""
+    if w.is_cuda and w.dtype in (torch.bfloat16, torch.float16):
+        if out is None:
+            return kernels().quantize_rows_e4m3(w)
+        kernels().quantize_rows_e4m3_out(w, out[0], out[1])
+        return out
+    from ..utils.fp8 import quantize_rows as definition
+
+    codes, scale = definition(w)
+    if out is None:
+        return codes, scale
+    out[0].copy_(codes)
+    out[1].copy_(scale)
+    return out
+
+
+def gemv_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
+            residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[N] = scale[n] * (codes[N, K] x[K]) (+ residual[N])."""
+    if _w8_native(x, codes):
+        return kernels().gemv_w8(x, codes, scale, None if residual is None else residual.contiguous())
+    from ..utils.fp8 import decode
+
+    y = torch.mv(decode(codes).to(x.dtype), x) * scale.to(x.dtype)
+    return y if residual is None else y + residual
+
+
+def gemv_swiglu_w8(x: torch.Tensor, codes13: torch.Tensor, scale13: torch.Tensor) -> torch.Tensor:
+    """a[H] = silu(g) * u with [g; u] = ``gemv_w8(x, codes13, scale13)`` on the fused [w1; w3] codes."""
+    if _w8_native(x, codes13):
+        return kernels().gemv_swiglu_w8(x, codes13, scale13)
+    return swiglu_reference(gemv_w8(x, codes13, scale13))
+
+
+def gemv_rows_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
+                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[R, N]; row r equals ``gemv_w8(x[r], codes, scale, residual[r])``."""
+    if _w8_native(x, codes):
+        return kernels().gemv_rows_w8(x, codes, scale, None if residual is None else residual.contiguous())
+    return torch.stack([gemv_w8(x[r], codes, scale, None if residual is None else residual[r])
+                        for r in range(x.shape[0])])
+
+
+def gemv_swiglu_rows_w8(x: torch.Tensor, codes13: torch.Tensor, scale13: torch.Tensor) -> torch.Tensor:
+    """a[R, H]; row r equals ``gemv_swiglu_w8(x[r], codes13, scale13)``."""
+    if _w8_native(x, codes13):
+        return kernels().gemv_swiglu_rows_w8(x, codes13, scale13)
+    return torch.stack([gemv_swiglu_w8(x[r], codes13, scale13) for r in range(x.shape[0])])
+
+
 def qkv_append_rows_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, t: int,
                      k_cache: torch.Tensor, v_cache: torch.Tensor, positions: Sequence[int]) -> None:
     """``qkv_append_`` on row b of qkv [B, (Hq + 2 Hkv) D] at position ``pos0[b] + t`` of the caches
