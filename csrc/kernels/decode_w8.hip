@@ -25,7 +25,7 @@
 // order of the adds.
 //
 // Plain vector code: no matrix cores, no atomics, and no inline assembly but for the empty register
-// barrier (no instruction in it) in scaled() below, which says why it is there. Every reduction has a fixed
+// barrier (no instruction in it) in scaled() of fp8.h, which says why it is there. Every reduction has a fixed
 // order, so each op returns the same bits from run to run.
 #include <climits>
 
@@ -47,21 +47,6 @@ __device__ __forceinline__ float dot16(const float* wf, const uint4& x0, const u
 #pragma unroll
   for (int j = 0; j < W8_VEC; ++j) acc = fmaf(wf[j], xf[j], acc);
   return acc;
-}
-
-// s * scale (+ residual): separately rounded fp32 operations. Each result passes an opaque register
-// barrier (the empty asm of common.h's pin8), so the compiler can neither contract the two into one
-// fma nor merge the last of them with the caller's conversion to fp16 into a mixed-precision fma
-// (v_fma_mixlo_f16), which rounds once where the definition rounds to fp32 first.
-template <class E>
-__device__ __forceinline__ float scaled(float s, float scale, const typename E::T* res) {
-  float v = s * scale;
-  asm volatile("" : "+v"(v));
-  if (res != nullptr) {
-    v = v + ld1<E>(res);
-    asm volatile("" : "+v"(v));
-  }
-  return v;
 }
 
 template <int RT>

@@ -46,3 +46,18 @@ __device__ __forceinline__ uint32_t f32x2_to_fp8(float a, float b) {
 __device__ __forceinline__ uint32_t f32x4_to_fp8(const float* f) {
   return f32x2_to_fp8(f[0], f[1]) | (f32x2_to_fp8(f[2], f[3]) << 16);
 }
+
+// s * scale (+ residual): separately rounded fp32 operations. Each result passes an opaque register
+// barrier (the empty asm of common.h's pin8), so the compiler can neither contract the two into one
+// fma nor merge the last of them with the caller's conversion to fp16 into a mixed-precision fma
+// (v_fma_mixlo_f16), which rounds once where the definition rounds to fp32 first.
+template <class E>
+__device__ __forceinline__ float scaled(float s, float scale, const typename E::T* res) {
+  float v = s * scale;
+  asm volatile("" : "+v"(v));
+  if (res != nullptr) {
+    v = v + ld1<E>(res);
+    asm volatile("" : "+v"(v));
+  }
+  return v;
+}

@@ -23,6 +23,12 @@ instead of about nine launches per layer issued from Python. The ids are the sam
 (``generation.Fp8Weights``: e4m3 codes, one fp32 scale per output row), built once after the checkpoint
 (or its ``ema`` entry) is loaded; one line on stderr gives the quantize time and the bytes. The prompt is
 still prefilled with the model's own weights.
+
+``--decode-mma`` (batched runs: ``--num-samples`` / ``--prompts-file``) runs the five products of a decode
+step on the matrix-core kernels (``generation.generate_batch(..., mma=True)``): one pass over the weights
+for up to 64 rows. A row's tokens still do not depend on its batch, but they are not bit for bit those of
+the default kernels (the sums run in another order). It composes with ``--weight-dtype fp8`` and
+``--decode-graph``; on ``--device cpu`` it changes nothing.
 """
 from __future__ import annotations
 
@@ -75,6 +81,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Weights the decode steps read: `model` (the checkpoint's, in --model-dtype) or `fp8` "
                    "(weight-only e4m3 with one scale per output row, quantized once after loading: half the bytes "
                    "per token; bf16 / fp16 models on the GPU, any dtype but fp32 on --device cpu)")
+    p.add_argument("--decode-mma", action="store_true",
+                   help="Batched runs (--num-samples / --prompts-file): the products of a decode step on the "
+                   "matrix-core kernels, whose time does not grow with the rows (bf16 / fp16 models on the GPU; on "
+                   "--device cpu it changes nothing). Off by default: the ids may differ from the default kernels'")
     p.add_argument("--json", action="store_true", help="Print one JSON line instead of the text")
     return p
 
@@ -111,6 +121,10 @@ def main(argv=None) -> int:
                                                                        and args.model_dtype not in ("bf16", "fp16"))):
         return _fail(f"--weight-dtype fp8 needs --model-dtype bf16 or fp16 on the GPU (on --device cpu: any but fp32), "
                      f"got {args.model_dtype} on {args.device}")
+    if args.decode_mma and args.device == "cuda" and args.model_dtype not in ("bf16", "fp16"):
+        return _fail(f"--decode-mma needs --model-dtype bf16 or fp16 on the GPU, got {args.model_dtype}")
+    if args.decode_mma and args.prompts_file is None and args.num_samples == 1:
+        return _fail("--decode-mma applies to batched runs: give --num-samples above 1 or --prompts-file")
     if args.prompt_ids_file and args.prompts_file is None:
         return _fail("--prompt-ids-file needs --prompts-file")
     lines = None
@@ -211,7 +225,8 @@ def main(argv=None) -> int:
         if batched:
             rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                   key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
-                                  graph=args.decode_graph, top_p=args.top_p, weights=weights)
+                                  graph=args.decode_graph, top_p=args.top_p, weights=weights,
+                                  mma=args.decode_mma)
         else:
             ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                            key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,

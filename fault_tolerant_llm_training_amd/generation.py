@@ -44,6 +44,15 @@ form on the same activations (``csrc/kernels/decode_w8.hip``) and nothing else c
 the training forward kernels on the model's own weights (it is bound by compute, and it is the code the
 trainer runs), so the prompt's K/V and the logits after the prompt come from the unquantized weights.
 With ``weights=None`` every path returns the bits it returned before.
+
+Matrix-core decode (``mma=True`` of :func:`decode_step_rows`, :class:`DecodeGraph` and
+:func:`generate_batch`): the ``gemv_rows`` kernels repeat every dot product per row, so a step's time
+grows with the batch although the weight bytes do not. With ``mma=True`` the five products run on the
+skinny GEMM kernels of ``csrc/kernels/decode_mma.hip`` (``D.gemm_rows_mma`` and its SwiGLU / ``_w8``
+forms; it composes with ``weights`` and ``graph``). They keep the batch invariance -- a row's logits do not
+depend on the batch it is in -- but add in another order than the one-row kernels, so the ids are those of
+``generate_batch([prompt], mma=True)``, not bit for bit those of :func:`generate`; that is why the
+default is off. On the CPU the argument changes nothing; an fp32 or fp64 model on the GPU is refused.
 """
 from __future__ import annotations
 
@@ -212,12 +221,22 @@ def _mv_swiglu(x, w13, q):
     return D.gemv_swiglu(x, w13) if q is None else D.gemv_swiglu_w8(x, q[0], q[1])
 
 
-def _mv_rows(x, w, q):
+def _mv_rows(x, w, q, mma=False):
+    if mma:
+        return D.gemm_rows_mma(x, w) if q is None else D.gemm_rows_mma_w8(x, q[0], q[1])
     return D.gemv_rows(x, w) if q is None else D.gemv_rows_w8(x, q[0], q[1])
 
 
-def _mv_swiglu_rows(x, w13, q):
+def _mv_swiglu_rows(x, w13, q, mma=False):
+    if mma:
+        return D.gemm_swiglu_rows_mma(x, w13) if q is None else D.gemm_swiglu_rows_mma_w8(x, q[0], q[1])
     return D.gemv_swiglu_rows(x, w13) if q is None else D.gemv_swiglu_rows_w8(x, q[0], q[1])
+
+
+def _check_mma(model, mma: bool) -> None:
+    flat = model.flat
+    if mma and flat.device.type == "cuda" and flat.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"mma=True needs a bf16 or fp16 model on the GPU, got {flat.dtype}")
 
 
 def _check_weights(model, weights: Optional[Fp8Weights]) -> None:
@@ -313,13 +332,15 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache,
     return _final_logits(model, h, d, weights)
 
 
-def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional[Fp8Weights] = None) -> torch.Tensor:
+def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional[Fp8Weights] = None,
+               mma: bool = False) -> torch.Tensor:
     """One pass over the weights for the B rows of ``tok`` [B, 1]: embedding, the layers, final norm and
     head; returns the logits [B, V]. The two ops that touch the cache are the caller's: ``append(i, qkv)``
     rotates Q in place and stores layer i's K and V, ``attend(i, q)`` returns its attention output
     [B, Hq D]. ``wait(range)`` is the parameter-gate wait before each range of weights (None: the caller
-    has waited for all of them). ``weights``: the products read these FP8 weights instead of the model's.
-    :func:`decode_step_rows` and :class:`DecodeGraph` share this loop."""
+    has waited for all of them). ``weights``: the products read these FP8 weights instead of the model's;
+    ``mma``: they run on the matrix-core kernels. :func:`decode_step_rows` and :class:`DecodeGraph` share
+    this loop."""
     a = model.model_args
     ln = a.norm_type == "layernorm"
     hq, hd = a.n_heads, a.head_dim
@@ -337,27 +358,29 @@ def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = _mv_rows(xn, at.wqkv, qqkv)
+        qkv = _mv_rows(xn, at.wqkv, qqkv, mma)
         append(i, qkv)
         o = attend(i, qkv[:, : hq * hd])
-        da = _mv_rows(o, at.wo.weight, qo)
+        da = _mv_rows(o, at.wo.weight, qo, mma)
         h, hn = Fx.add_norm(h, da, layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = _mv_rows(_mv_swiglu_rows(hn, ff.w13, q13), ff.w2.weight, q2)
+        d = _mv_rows(_mv_swiglu_rows(hn, ff.w13, q13, mma), ff.w2.weight, q2, mma)
     if wait is not None:
         wait(final_r)
     if d is None:
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return _mv_rows(hn, model.output.weight, None if weights is None else weights.head)
+    return _mv_rows(hn, model.output.weight, None if weights is None else weights.head, mma)
 
 
 @torch.no_grad()
 def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: BatchKVCache, t: int,
-                     weights: Optional[Fp8Weights] = None) -> torch.Tensor:
+                     weights: Optional[Fp8Weights] = None, mma: bool = False) -> torch.Tensor:
     """Decode step ``t`` (0, 1, ...) of a batch: append ``tokens[b]`` at position ``pos0[b] + t`` of
-    row ``b``; returns the logits [B, V] after them. The loop of :func:`decode_step` on B rows."""
+    row ``b``; returns the logits [B, V] after them. The loop of :func:`decode_step` on B rows.
+    ``mma``: the products on the matrix-core kernels (up to 64 rows)."""
     _check_weights(model, weights)
+    _check_mma(model, mma)
     B, t = cache.batch, int(t)
     if t != cache.steps:
         raise ValueError(f"decode step {t} out of order (the cache has taken {cache.steps})")
@@ -372,7 +395,7 @@ def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: B
     logits = _rows_pass(
         model, tok,
         lambda i, qkv: D.qkv_append_rows_(qkv, cos, sin, pos0, t, cache.k[i], cache.v[i], lengths),
-        lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait, weights)
+        lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait, weights, mma)
     cache.steps = t + 1
     return logits
 
@@ -413,13 +436,17 @@ class DecodeGraph:
     The capture happens here, once (``captures`` counts them), so build the object when the parameters'
     addresses are final. :meth:`run` serves any request of up to ``batch`` rows that fits ``max_len``.
     With ``weights`` (:class:`Fp8Weights`) the captured products are the ``_w8`` ops on its buffers; the
-    prefill of every call still runs on the model's own weights."""
+    prefill of every call still runs on the model's own weights. With ``mma`` the captured products are the
+    matrix-core ops (``batch`` up to 64)."""
 
     EOS_CHECK_EVERY = 16  # tokens between two looks at the generated ids (one copy to the host each)
 
-    def __init__(self, model, batch: int, max_len: int, weights: Optional[Fp8Weights] = None):
+    def __init__(self, model, batch: int, max_len: int, weights: Optional[Fp8Weights] = None, mma: bool = False):
         flat, a = model.flat, model.model_args
         _check_weights(model, weights)
+        _check_mma(model, mma)
+        if mma and int(batch) > MAX_BATCH:
+            raise ValueError(f"mma=True takes up to {MAX_BATCH} rows, got {batch}")
         if not graph_supported(model):  # before anything is allocated or a capture opens
             raise ValueError("DecodeGraph needs a GPU model of a kernel dtype (bf16, fp16 or fp32) whose vocabulary "
                              f"is a multiple of 8 (the device sampler's rows), got {flat.device.type} / {flat.dtype} "
@@ -427,6 +454,7 @@ class DecodeGraph:
         dev = flat.device
         self.model = model
         self.weights = weights
+        self.mma = bool(mma)
         self.cache = BatchKVCache(a, batch, max_len, dev, flat.dtype)
         self.batch, self.max_len = self.cache.batch, self.cache.max_len
         B = self.batch
@@ -459,7 +487,7 @@ class DecodeGraph:
             model, self.tok,
             lambda i, qkv: D.qkv_append_rows_dev_(qkv, cos, sin, pos0, ctl, cache.k[i], cache.v[i]),
             lambda i, q: D.attn_rows_dev(q, cache.k[i], cache.v[i], pos0, ctl, self.part, self.o), None,
-            self.weights)
+            self.weights, self.mma)
         self.logits.copy_(logits)
         D.ctl_advance_(ctl)
 
@@ -562,7 +590,7 @@ MAX_BATCH = 64
 def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0,
                    top_k: int = 0, key: int = 0, eos_id: Optional[int] = None, step: int = 0,
                    graph: bool = False, top_p: float = 1.0,
-                   weights: Optional[Fp8Weights] = None) -> List[List[int]]:
+                   weights: Optional[Fp8Weights] = None, mma: bool = False) -> List[List[int]]:
     """:func:`generate` for B prompts at once: the ids generated after each of ``prompts``. New token
     ``t`` of every row comes from one ``D.sample(logits[B, V], ..., token_key(key, t), step)``, row
     ``b``'s draw being the sampler's row ``b``: row 0 equals ``generate`` with the same arguments, and
@@ -571,8 +599,11 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     row's draw or position shifts. Identical prompts are prefilled once. ``graph=True`` decodes with a
     :class:`DecodeGraph` built for this request (the same ids; keep the object yourself to reuse its
     capture). ``weights``: decode with these FP8 weights (the prompts' K/V and the first token's logits
-    come from the prefill, on the unquantized weights)."""
+    come from the prefill, on the unquantized weights). ``mma``: the decode products on the matrix-core
+    kernels: a row's ids still do not depend on its batch, but they are those of
+    ``generate_batch([prompt], ..., mma=True)``, not bit for bit those of :func:`generate`."""
     _check_weights(model, weights)
+    _check_mma(model, mma)
     rows = [[int(t) for t in p] for p in prompts]
     n_new = int(max_new_tokens)
     a = model.model_args
@@ -585,7 +616,7 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
         return [[] for _ in rows]
     flat = model.flat
     if graph and graph_supported(model):
-        return DecodeGraph(model, B, max(len(p) for p in rows) + n_new, weights).run(
+        return DecodeGraph(model, B, max(len(p) for p in rows) + n_new, weights, mma).run(
             rows, n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id, top_p=top_p)
     cache = BatchKVCache(a, B, max(len(p) for p in rows) + n_new, flat.device, flat.dtype)
     logits = _prefill_rows(model, rows, cache)
@@ -599,7 +630,7 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
                 live[b] = eos_id is None or tok != eos_id
         if not any(live) or t == n_new - 1:
             break
-        logits = decode_step_rows(model, nxt, cache, t, weights)
+        logits = decode_step_rows(model, nxt, cache, t, weights, mma)
     return out
 
 

@@ -166,6 +166,57 @@ def gemv_swiglu_rows_w8(x: torch.Tensor, codes13: torch.Tensor, scale13: torch.T
     return torch.stack([gemv_swiglu_w8(x[r], codes13, scale13) for r in range(x.shape[0])])
 
 
+# ---------------------------------------------------------------------------------------------
+# The matrix-core forms (csrc/kernels/decode_mma.hip): the products of the multi-row ops above for
+# 1 <= R <= 64 rows on v_mfma_f32_16x16x32, one pass over the weight whatever R is. Their contract is
+# batch invariance -- row r of the result depends on x[r] and the weight alone, not on R, the other
+# rows or the row's place -- and equal bits from run to run; the sums run in another order than the
+# gemv kernels', so the bits are not those of the ``_rows`` ops. ``split`` (0: chosen from the weight's
+# shape alone) is the number of K slices whose fp32 partials are added in slice order; the invariance
+# holds for any one value of it. The route is chosen as for the ``_w8`` ops: GPU tensors of bf16 / fp16
+# run the kernels and an operand they cannot take is an error of the op's host checks; fp32 and fp64
+# tensors on the GPU raise here; CPU tensors take the ``_rows`` ops' composed definitions.
+# ---------------------------------------------------------------------------------------------
+def _mma_native(op: str, x: torch.Tensor, w: torch.Tensor) -> bool:
+    if not (x.is_cuda or w.is_cuda):
+        return False
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{op}: the matrix-core kernels take bf16 or fp16 activations on the GPU, got {x.dtype}")
+    return True
+
+
+def gemm_rows_mma(x: torch.Tensor, w: torch.Tensor, residual: Optional[torch.Tensor] = None,
+                  split: int = 0) -> torch.Tensor:
+    """y[R, N] = x[R, K] w[N, K]^T (+ residual[R, N])."""
+    if _mma_native("gemm_rows_mma", x, w):
+        return kernels().gemm_rows_mma(x, w, None if residual is None else residual.contiguous(), int(split))
+    return gemv_rows(x, w, residual)
+
+
+def gemm_swiglu_rows_mma(x: torch.Tensor, w13: torch.Tensor, split: int = 0) -> torch.Tensor:
+    """a[R, H] = silu(g) * u with [g, u] = ``gemm_rows_mma(x, w13)``, bit for bit."""
+    if _mma_native("gemm_swiglu_rows_mma", x, w13):
+        return kernels().gemm_swiglu_rows_mma(x, w13, int(split))
+    return gemv_swiglu_rows(x, w13)
+
+
+def gemm_rows_mma_w8(x: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor,
+                     residual: Optional[torch.Tensor] = None, split: int = 0) -> torch.Tensor:
+    """y[R, N] = scale[n] * (x[R, K] decode(codes)[N, K]^T) (+ residual[R, N])."""
+    if _mma_native("gemm_rows_mma_w8", x, codes):
+        return kernels().gemm_rows_mma_w8(x, codes, scale, None if residual is None else residual.contiguous(),
+                                          int(split))
+    return gemv_rows_w8(x, codes, scale, residual)
+
+
+def gemm_swiglu_rows_mma_w8(x: torch.Tensor, codes13: torch.Tensor, scale13: torch.Tensor,
+                            split: int = 0) -> torch.Tensor:
+    """a[R, H] = silu(g) * u with [g, u] = ``gemm_rows_mma_w8(x, codes13, scale13)``, bit for bit."""
+    if _mma_native("gemm_swiglu_rows_mma_w8", x, codes13):
+        return kernels().gemm_swiglu_rows_mma_w8(x, codes13, scale13, int(split))
+    return gemv_swiglu_rows_w8(x, codes13, scale13)
+
+
 def qkv_append_rows_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, t: int,
                      k_cache: torch.Tensor, v_cache: torch.Tensor, positions: Sequence[int]) -> None:
     """``qkv_append_`` on row b of qkv [B, (Hq + 2 Hkv) D] at position ``pos0[b] + t`` of the caches
