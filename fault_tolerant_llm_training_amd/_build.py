@@ -122,7 +122,10 @@ W4_CHECKED = ("gemm_w4_fwd", "gemm_w4_dx", "gemm_w4_dw")
 # 256 with spills to scratch. Without them every kernel of the unit stays at or under 128 VGPRs with
 # no scratch, which the 512-thread workgroups of the multi-row forms need to fit twice per CU. The
 # two builds were compared by their register counts only, not timed against each other. The other
-# units keep the flags they were tuned with.
+# units keep the flags they were tuned with. decode_mx4 is not in the list: its products are dot2
+# instructions, the only fp32 the compiler packs is the block sums' add and scale fma across the rows of a
+# tile (8 rows: 16 v_pk_add_f32, 16 v_pk_fma_f32), and with that every kernel of the unit is without scratch (plain forms 75-102
+# VGPRs, SwiGLU 113-148).
 NO_PACKED_FP32 = ("decode_w8",)
 NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 

@@ -77,10 +77,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--use-ema", action="store_true",
                    help="Generate from the file's `ema` entry (the parameter average of a --ema-decay run), rounded "
                    "to nearest in --model-dtype, instead of `model`; an error if the file has none")
-    p.add_argument("--weight-dtype", type=str, default="model", choices=["model", "fp8"],
-                   help="Weights the decode steps read: `model` (the checkpoint's, in --model-dtype) or `fp8` "
+    p.add_argument("--weight-dtype", type=str, default="model", choices=["model", "fp8", "mxfp4"],
+                   help="Weights the decode steps read: `model` (the checkpoint's, in --model-dtype), `fp8` "
                    "(weight-only e4m3 with one scale per output row, quantized once after loading: half the bytes "
-                   "per token; bf16 / fp16 models on the GPU, any dtype but fp32 on --device cpu)")
+                   "per token) or `mxfp4` (weight-only OCP MXFP4, e2m1 with one power-of-two scale per 32 elements: "
+                   "0.53 bytes per weight; not with --decode-mma). Both: bf16 / fp16 models on the GPU, any dtype "
+                   "but fp32 on --device cpu")
     p.add_argument("--decode-mma", action="store_true",
                    help="Batched runs (--num-samples / --prompts-file): the products of a decode step on the "
                    "matrix-core kernels, whose time does not grow with the rows (bf16 / fp16 models on the GPU; on "
@@ -121,6 +123,12 @@ def main(argv=None) -> int:
                                                                        and args.model_dtype not in ("bf16", "fp16"))):
         return _fail(f"--weight-dtype fp8 needs --model-dtype bf16 or fp16 on the GPU (on --device cpu: any but fp32), "
                      f"got {args.model_dtype} on {args.device}")
+    if args.weight_dtype == "mxfp4" and (args.model_dtype == "fp32" or (args.device == "cuda"
+                                                                         and args.model_dtype not in ("bf16", "fp16"))):
+        return _fail(f"--weight-dtype mxfp4 needs --model-dtype bf16 or fp16 on the GPU (on --device cpu: any but "
+                     f"fp32), got {args.model_dtype} on {args.device}")
+    if args.weight_dtype == "mxfp4" and args.decode_mma:
+        return _fail("--decode-mma has no MXFP4 kernels: drop it, or use --weight-dtype fp8 or model")
     if args.decode_mma and args.device == "cuda" and args.model_dtype not in ("bf16", "fp16"):
         return _fail(f"--decode-mma needs --model-dtype bf16 or fp16 on the GPU, got {args.model_dtype}")
     if args.decode_mma and args.prompts_file is None and args.num_samples == 1:
@@ -206,17 +214,17 @@ def main(argv=None) -> int:
     model.eval()
     eos = getattr(tok, "eos_token_id", None) if tok is not None else None
     weights = None
-    if args.weight_dtype == "fp8":
-        from .generation import Fp8Weights
+    if args.weight_dtype != "model":
+        from .generation import Fp8Weights, Mxfp4Weights
 
         tq = time.perf_counter()
         try:
-            weights = Fp8Weights(model)
+            weights = (Fp8Weights if args.weight_dtype == "fp8" else Mxfp4Weights)(model)
         except ValueError as e:
             return _fail(str(e))
         if device.type == "cuda":
             torch.cuda.synchronize()
-        print(f"generate: fp8 weights: {weights.nbytes / 2 ** 20:.1f} MiB of codes and scales, quantized in "
+        print(f"generate: {args.weight_dtype} weights: {weights.nbytes / 2 ** 20:.1f} MiB of codes and scales, quantized in "
               f"{time.perf_counter() - tq:.3f} s", file=sys.stderr, flush=True)
     if device.type == "cuda":
         torch.cuda.synchronize()

@@ -45,6 +45,11 @@ the training forward kernels on the model's own weights (it is bound by compute,
 trainer runs), so the prompt's K/V and the logits after the prompt come from the unquantized weights.
 With ``weights=None`` every path returns the bits it returned before.
 
+Weight-only MXFP4 (:class:`Mxfp4Weights`, the same ``weights`` argument): e2m1 codes with one
+power-of-two scale per 32 elements along K (``utils/mxfp4.py``), 0.53 bytes per weight; the products
+become the ``_mx4`` ops (``csrc/kernels/decode_mx4.hip``) and the rest is as for FP8. It has no
+matrix-core form: ``mma=True`` with it raises.
+
 Matrix-core decode (``mma=True`` of :func:`decode_step_rows`, :class:`DecodeGraph` and
 :func:`generate_batch`): the ``gemv_rows`` kernels repeat every dot product per row, so a step's time
 grows with the batch although the weight bytes do not. With ``mma=True`` the five products run on the
@@ -171,17 +176,20 @@ class Fp8Weights:
     the composed definitions, which would silently stand in for a kernel), and any weight whose K is
     not a multiple of 16 (the codes move in 16-byte vectors)."""
 
+    K_MULTIPLE, K_WHY = 16, "16-byte vectors of e4m3 codes"
+    _quantize = staticmethod(D.quantize_rows)
+
     def __init__(self, model):
-        flat = model.flat
+        flat, who = model.flat, type(self).__name__
         if flat.dtype == torch.float32 or (flat.device.type == "cuda"
                                            and flat.dtype not in (torch.bfloat16, torch.float16)):
-            raise ValueError(f"Fp8Weights needs a bf16 or fp16 model on the GPU (on the CPU: any dtype but fp32), "
+            raise ValueError(f"{who} needs a bf16 or fp16 model on the GPU (on the CPU: any dtype but fp32), "
                              f"got {flat.device.type} / {flat.dtype}")
         self.model = model
         for name, w in self._sources():
-            if w.dim() != 2 or w.shape[1] % 16 != 0:
-                raise ValueError(f"Fp8Weights: {name} has shape {tuple(w.shape)}; K must be a multiple of 16 "
-                                 "(16-byte vectors of e4m3 codes)")
+            if w.dim() != 2 or w.shape[1] % self.K_MULTIPLE != 0:
+                raise ValueError(f"{who}: {name} has shape {tuple(w.shape)}; K must be a multiple of "
+                                 f"{self.K_MULTIPLE} ({self.K_WHY})")
         self.layers: List[tuple] = []
         self.head: Optional[tuple] = None
         self.requantize()
@@ -202,7 +210,7 @@ class Fp8Weights:
         for r in (emb_r, *layer_r, final_r):
             self.model._wait(r)
         old = [q for layer in self.layers for q in layer] + ([self.head] if self.head is not None else [])
-        new = [D.quantize_rows(w, old[j] if old else None) for j, (_, w) in enumerate(self._sources())]
+        new = [self._quantize(w, old[j] if old else None) for j, (_, w) in enumerate(self._sources())]
         self.layers = [tuple(new[4 * i : 4 * i + 4]) for i in range(len(new) // 4)]
         self.head = new[-1]
 
@@ -212,36 +220,59 @@ class Fp8Weights:
                    for layer in (*self.layers, (self.head,)) for c, s in layer)
 
 
-# One product of a pass: the model's weight, or its FP8 pair ``q`` (``(codes, scale)``) where given.
-def _mv(x, w, q):
-    return D.gemv(x, w) if q is None else D.gemv_w8(x, q[0], q[1])
+class Mxfp4Weights(Fp8Weights):
+    """The decode weights of ``model`` in weight-only MXFP4 (``utils/mxfp4.py``): e2m1 codes, two per byte,
+    and one e8m0 scale byte per 32 elements along K -- 0.53 bytes per weight -- quantized by
+    ``D.quantize_rows_mx4``; the products of a pass become the ``_mx4`` ops
+    (``csrc/kernels/decode_mx4.hip``). The interface is :class:`Fp8Weights`': ``layers``, ``head`` (each
+    a ``(codes, scales)`` pair), :meth:`requantize` in place, ``nbytes``; so are the refusals, with K a
+    multiple of 32 (one scale per block). There are no matrix-core kernels for it: ``mma=True`` raises."""
+
+    K_MULTIPLE, K_WHY = 32, "one MXFP4 scale per block of 32 elements"
+    _quantize = staticmethod(D.quantize_rows_mx4)
 
 
-def _mv_swiglu(x, w13, q):
-    return D.gemv_swiglu(x, w13) if q is None else D.gemv_swiglu_w8(x, q[0], q[1])
+# One product of a pass: the model's weight, or its quantized pair ``q`` (``(codes, scale)`` of an
+# :class:`Fp8Weights`, ``(codes, scales)`` of an :class:`Mxfp4Weights`: ``mx4`` says which) where given.
+def _mv(x, w, q, mx4=False):
+    if q is None:
+        return D.gemv(x, w)
+    return D.gemv_mx4(x, q[0], q[1]) if mx4 else D.gemv_w8(x, q[0], q[1])
 
 
-def _mv_rows(x, w, q, mma=False):
+def _mv_swiglu(x, w13, q, mx4=False):
+    if q is None:
+        return D.gemv_swiglu(x, w13)
+    return D.gemv_swiglu_mx4(x, q[0], q[1]) if mx4 else D.gemv_swiglu_w8(x, q[0], q[1])
+
+
+def _mv_rows(x, w, q, mma=False, mx4=False):
+    if mx4 and q is not None:  # _check_mma has refused mma
+        return D.gemv_rows_mx4(x, q[0], q[1])
     if mma:
         return D.gemm_rows_mma(x, w) if q is None else D.gemm_rows_mma_w8(x, q[0], q[1])
     return D.gemv_rows(x, w) if q is None else D.gemv_rows_w8(x, q[0], q[1])
 
 
-def _mv_swiglu_rows(x, w13, q, mma=False):
+def _mv_swiglu_rows(x, w13, q, mma=False, mx4=False):
+    if mx4 and q is not None:
+        return D.gemv_swiglu_rows_mx4(x, q[0], q[1])
     if mma:
         return D.gemm_swiglu_rows_mma(x, w13) if q is None else D.gemm_swiglu_rows_mma_w8(x, q[0], q[1])
     return D.gemv_swiglu_rows(x, w13) if q is None else D.gemv_swiglu_rows_w8(x, q[0], q[1])
 
 
-def _check_mma(model, mma: bool) -> None:
+def _check_mma(model, mma: bool, weights: Optional[Fp8Weights] = None) -> None:
     flat = model.flat
+    if mma and isinstance(weights, Mxfp4Weights):
+        raise ValueError("mma=True has no MXFP4 kernels: decode Mxfp4Weights with mma=False")
     if mma and flat.device.type == "cuda" and flat.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"mma=True needs a bf16 or fp16 model on the GPU, got {flat.dtype}")
 
 
 def _check_weights(model, weights: Optional[Fp8Weights]) -> None:
     if weights is not None and weights.model is not model:
-        raise ValueError("these Fp8Weights were quantized from another model")
+        raise ValueError(f"these {type(weights).__name__} were quantized from another model")
 
 
 def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor],
@@ -254,7 +285,8 @@ def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor],
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return _mv(hn.reshape(-1), model.output.weight, None if weights is None else weights.head)
+    return _mv(hn.reshape(-1), model.output.weight, None if weights is None else weights.head,
+               isinstance(weights, Mxfp4Weights))
 
 
 @torch.no_grad()
@@ -313,6 +345,7 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache,
     model._wait(emb_r)
     h = Fx.embedding(tok, model.tok_embeddings.weight, None).view(1, -1)
     cos, sin = model.rope_cos, model.rope_sin
+    mx4 = isinstance(weights, Mxfp4Weights)
     d = None
     for i, layer in enumerate(model.layers.values()):
         model._wait(layer_r[i])
@@ -322,12 +355,12 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache,
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = _mv(xn.reshape(-1), at.wqkv, qqkv)
+        qkv = _mv(xn.reshape(-1), at.wqkv, qqkv, mx4)
         D.qkv_append_(qkv, cos, sin, pos, cache.k[i], cache.v[i])
         o = D.attn(qkv[: hq * hd], cache.k[i], cache.v[i], pos + 1)
-        da = _mv(o, at.wo.weight, qo)
+        da = _mv(o, at.wo.weight, qo, mx4)
         h, hn = Fx.add_norm(h, da.view(1, -1), layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = _mv(_mv_swiglu(hn.reshape(-1), ff.w13, q13), ff.w2.weight, q2).view(1, -1)
+        d = _mv(_mv_swiglu(hn.reshape(-1), ff.w13, q13, mx4), ff.w2.weight, q2, mx4).view(1, -1)
     cache.length = pos + 1
     return _final_logits(model, h, d, weights)
 
@@ -345,6 +378,7 @@ def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional
     ln = a.norm_type == "layernorm"
     hq, hd = a.n_heads, a.head_dim
     emb_r, layer_r, final_r = model._ranges
+    mx4 = isinstance(weights, Mxfp4Weights)
     if wait is not None:
         wait(emb_r)
     h = Fx.embedding(tok, model.tok_embeddings.weight, None).view(tok.shape[0], -1)
@@ -358,19 +392,19 @@ def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = _mv_rows(xn, at.wqkv, qqkv, mma)
+        qkv = _mv_rows(xn, at.wqkv, qqkv, mma, mx4)
         append(i, qkv)
         o = attend(i, qkv[:, : hq * hd])
-        da = _mv_rows(o, at.wo.weight, qo, mma)
+        da = _mv_rows(o, at.wo.weight, qo, mma, mx4)
         h, hn = Fx.add_norm(h, da, layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = _mv_rows(_mv_swiglu_rows(hn, ff.w13, q13, mma), ff.w2.weight, q2, mma)
+        d = _mv_rows(_mv_swiglu_rows(hn, ff.w13, q13, mma, mx4), ff.w2.weight, q2, mma, mx4)
     if wait is not None:
         wait(final_r)
     if d is None:
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return _mv_rows(hn, model.output.weight, None if weights is None else weights.head, mma)
+    return _mv_rows(hn, model.output.weight, None if weights is None else weights.head, mma, mx4)
 
 
 @torch.no_grad()
@@ -380,7 +414,7 @@ def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: B
     row ``b``; returns the logits [B, V] after them. The loop of :func:`decode_step` on B rows.
     ``mma``: the products on the matrix-core kernels (up to 64 rows)."""
     _check_weights(model, weights)
-    _check_mma(model, mma)
+    _check_mma(model, mma, weights)
     B, t = cache.batch, int(t)
     if t != cache.steps:
         raise ValueError(f"decode step {t} out of order (the cache has taken {cache.steps})")
@@ -444,7 +478,7 @@ class DecodeGraph:
     def __init__(self, model, batch: int, max_len: int, weights: Optional[Fp8Weights] = None, mma: bool = False):
         flat, a = model.flat, model.model_args
         _check_weights(model, weights)
-        _check_mma(model, mma)
+        _check_mma(model, mma, weights)
         if mma and int(batch) > MAX_BATCH:
             raise ValueError(f"mma=True takes up to {MAX_BATCH} rows, got {batch}")
         if not graph_supported(model):  # before anything is allocated or a capture opens
@@ -603,7 +637,7 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     kernels: a row's ids still do not depend on its batch, but they are those of
     ``generate_batch([prompt], ..., mma=True)``, not bit for bit those of :func:`generate`."""
     _check_weights(model, weights)
-    _check_mma(model, mma)
+    _check_mma(model, mma, weights)
     rows = [[int(t) for t in p] for p in prompts]
     n_new = int(max_new_tokens)
     a = model.model_args

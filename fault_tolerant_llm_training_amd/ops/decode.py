@@ -167,6 +167,66 @@ def gemv_swiglu_rows_w8(x: torch.Tensor, codes13: torch.Tensor, scale13: torch.T
 
 
 # ---------------------------------------------------------------------------------------------
+# The weight-only MXFP4 forms (csrc/kernels/decode_mx4.hip): the weight is e2m1 codes, two per byte
+# (uint8 [N, K / 2]), with one e8m0 scale byte per block of 32 elements (uint8 [N, K / 32]), as
+# ``utils.mxfp4`` defines them. The route is chosen as for the ``_w8`` ops, by device and dtype alone:
+# GPU tensors of a 16-bit kernel dtype run the kernels, and an operand they cannot take is an error of
+# the op's host checks; CPU tensors and fp64 take the composed definition: ``dequant`` in x's dtype and
+# ``mv``, nothing else, since the scales are inside ``dequant``.
+# ---------------------------------------------------------------------------------------------
+def quantize_rows_mx4(w: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """``(codes, scales)`` of ``w [N, K]`` (``utils.mxfp4.quantize_rows``); with ``out`` given, written
+    into that pair in place."""
+    if w.is_cuda and w.dtype in (torch.bfloat16, torch.float16):
+        if out is None:
+            return kernels().quantize_rows_mxfp4(w)
+        kernels().quantize_rows_mxfp4_out(w, out[0], out[1])
+        return out
+    from ..utils.mxfp4 import quantize_rows as definition
+
+    codes, scales = definition(w)
+    if out is None:
+        return codes, scales
+    out[0].copy_(codes)
+    out[1].copy_(scales)
+    return out
+
+
+def gemv_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+             residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[N] = dequant(codes, scales)[N, K] x[K] (+ residual[N])."""
+    if _w8_native(x, codes):
+        return kernels().gemv_mx4(x, codes, scales, None if residual is None else residual.contiguous())
+    from ..utils.mxfp4 import dequant
+
+    y = torch.mv(dequant(codes, scales).to(x.dtype), x)
+    return y if residual is None else y + residual
+
+
+def gemv_swiglu_mx4(x: torch.Tensor, codes13: torch.Tensor, scales13: torch.Tensor) -> torch.Tensor:
+    """a[H] = silu(g) * u with [g; u] = ``gemv_mx4(x, codes13, scales13)`` on the fused [w1; w3] codes."""
+    if _w8_native(x, codes13):
+        return kernels().gemv_swiglu_mx4(x, codes13, scales13)
+    return swiglu_reference(gemv_mx4(x, codes13, scales13))
+
+
+def gemv_rows_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor,
+                  residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[R, N]; row r equals ``gemv_mx4(x[r], codes, scales, residual[r])``."""
+    if _w8_native(x, codes):
+        return kernels().gemv_rows_mx4(x, codes, scales, None if residual is None else residual.contiguous())
+    return torch.stack([gemv_mx4(x[r], codes, scales, None if residual is None else residual[r])
+                        for r in range(x.shape[0])])
+
+
+def gemv_swiglu_rows_mx4(x: torch.Tensor, codes13: torch.Tensor, scales13: torch.Tensor) -> torch.Tensor:
+    """a[R, H]; row r equals ``gemv_swiglu_mx4(x[r], codes13, scales13)``."""
+    if _w8_native(x, codes13):
+        return kernels().gemv_swiglu_rows_mx4(x, codes13, scales13)
+    return torch.stack([gemv_swiglu_mx4(x[r], codes13, scales13) for r in range(x.shape[0])])
+
+
+# ---------------------------------------------------------------------------------------------
 # The matrix-core forms (csrc/kernels/decode_mma.hip): the products of the multi-row ops above for
 # 1 <= R <= 64 rows on v_mfma_f32_16x16x32, one pass over the weight whatever R is. Their contract is
 # batch invariance -- row r of the result depends on x[r] and the weight alone, not on R, the other
