@@ -36,28 +36,13 @@
 #include <climits>
 #include <type_traits>
 
+#include "decode_attn.h"  // LOG2E, DECODE_CHUNK, CTL_*, row_keys, the merge kernels (shared with decode_kv8.hip)
 #include "sround.h"
 #include "torch_utils.h"
 
 namespace {
 
-constexpr float LOG2E = 1.4426950408889634f;
-// keys per workgroup of decode_attn; the chunk partials are merged in chunk order
-constexpr int DECODE_CHUNK = 128;
 constexpr int SAMPLE_MAX_BLOCKS = 32768;
-
-// The control block of the device-step ops: int32 words (ops/decode.py keeps the same indices). The
-// host writes it once per call; the kernels only read it, but for decode_ctl_advance_ on CTL_T.
-enum : int {
-  CTL_T = 0,            // the decode step: new token t of the call
-  CTL_KEY_LO = 1,       // the call's sampler key (token_key is formed from it and t)
-  CTL_KEY_HI = 2,
-  CTL_STEP = 3,         // the sampler's step
-  CTL_TEMPERATURE = 4,  // float bits
-  CTL_TOP_K = 5,
-  CTL_TOP_P = 6,        // float bits; 0 (what a writer that knows no top-p leaves) or >= 1: off
-  CTL_WORDS = 8
-};
 
 // ---- one 16-byte vector of the model dtype: 8 elements (bf16 / fp16) or 4 (fp32)
 template <class E>
@@ -440,12 +425,6 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const typename E::T* _
   attn_chunk<E, D, GT>(q, kc, vc, part, hq, hkv, smax, n_keys, scale);
 }
 
-// The key count of row b of a batch: pos0[b] + t + 1, at most max_keys (which the host checked
-// against Smax; pos0 itself is never read back). Below 1 no workgroup of the row does anything.
-__device__ __forceinline__ int row_keys(const int* __restrict__ pos0, int b, int t, int max_keys) {
-  return (int)min((long)pos0[b] + t + 1, (long)max_keys);
-}
-
 // Grid (Hkv, ceil(max_keys / DECODE_CHUNK), B); q rows q_stride elements apart (the Q columns of a
 // qkv buffer, in place); part [B, gridDim.y, Hq, D + 2]. A workgroup whose chunk
 // starts at or beyond its row's key count leaves here, all of it, before the first barrier: its
@@ -486,59 +465,6 @@ __global__ __launch_bounds__(256) void decode_attn_rows_dev_kernel(const typenam
                                                                    const int* __restrict__ ctl, long q_stride,
                                                                    int hq, int hkv, long smax, float scale) {
   attn_rows_chunk<E, D, GT>(q, kc, vc, part, pos0, ctl[CTL_T], (int)smax, q_stride, hq, hkv, smax, scale);
-}
-
-// One workgroup per query head, one thread per dim: the chunk partials in chunk order.
-template <class E, int D>
-__device__ __forceinline__ void attn_merge(const float* __restrict__ part, typename E::T* __restrict__ o, int hq,
-                                           int nchunks) {
-  const int h = blockIdx.x, dd = threadIdx.x;
-  float M = -INFINITY, L = 0.f, A = 0.f;
-  for (int c = 0; c < nchunks; ++c) {
-    const float* pr = part + ((long)c * hq + h) * (D + 2);
-    const float m = pr[D], l = pr[D + 1], a = pr[dd];
-    const float nM = fmaxf(M, m);
-    const float f0 = exp2f((M - nM) * LOG2E), f1 = exp2f((m - nM) * LOG2E);
-    A = A * f0 + a * f1;
-    L = L * f0 + l * f1;
-    M = nM;
-  }
-  o[(long)h * D + dd] = cvt1<E>(A / L);
-}
-
-template <class E, int D>
-__global__ __launch_bounds__(D) void decode_attn_merge_kernel(const float* __restrict__ part,
-                                                              typename E::T* __restrict__ o, int hq,
-                                                              int nchunks) {
-  attn_merge<E, D>(part, o, hq, nchunks);
-}
-
-// Grid (Hq, B): row b folds its own ceil(keys / DECODE_CHUNK) chunks of part [B, max_chunks, Hq, D + 2].
-template <class E, int D>
-__device__ __forceinline__ void attn_merge_row(const float* __restrict__ part, typename E::T* __restrict__ o,
-                                               const int* __restrict__ pos0, int t, int max_keys, int max_chunks,
-                                               int hq) {
-  const int b = blockIdx.y;
-  const int n_keys = max(row_keys(pos0, b, t, max_keys), 0);
-  attn_merge<E, D>(part + (long)b * max_chunks * hq * (D + 2), o + (long)b * hq * D, hq,
-                   (n_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
-}
-
-template <class E, int D>
-__global__ __launch_bounds__(D) void decode_attn_merge_rows_kernel(const float* __restrict__ part,
-                                                                   typename E::T* __restrict__ o,
-                                                                   const int* __restrict__ pos0, int t,
-                                                                   int max_keys, int max_chunks, int hq) {
-  attn_merge_row<E, D>(part, o, pos0, t, max_keys, max_chunks, hq);
-}
-
-template <class E, int D>
-__global__ __launch_bounds__(D) void decode_attn_merge_rows_dev_kernel(const float* __restrict__ part,
-                                                                       typename E::T* __restrict__ o,
-                                                                       const int* __restrict__ pos0,
-                                                                       const int* __restrict__ ctl, int max_keys,
-                                                                       int max_chunks, int hq) {
-  attn_merge_row<E, D>(part, o, pos0, ctl[CTL_T], max_keys, max_chunks, hq);
 }
 
 // --------------------------------------------------------------------------------------------

@@ -29,6 +29,10 @@ step on the matrix-core kernels (``generation.generate_batch(..., mma=True)``): 
 for up to 64 rows. A row's tokens still do not depend on its batch, but they are not bit for bit those of
 the default kernels (the sums run in another order). It composes with ``--weight-dtype fp8`` and
 ``--decode-graph``; on ``--device cpu`` it changes nothing.
+
+``--kv-dtype fp8`` keeps the KV cache as e4m3 codes with one fp32 scale per stored head row
+(``generation.KVCache(..., kv_dtype="fp8")``): about half the cache bytes a step reads. The prompt's own
+attention still runs on the unquantized K and V.
 """
 from __future__ import annotations
 
@@ -87,6 +91,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="Batched runs (--num-samples / --prompts-file): the products of a decode step on the "
                    "matrix-core kernels, whose time does not grow with the rows (bf16 / fp16 models on the GPU; on "
                    "--device cpu it changes nothing). Off by default: the ids may differ from the default kernels'")
+    p.add_argument("--kv-dtype", type=str, default="model", choices=["model", "fp8"],
+                   help="What the KV cache holds: `model` (K and V in --model-dtype) or `fp8` (e4m3 codes with one "
+                   "fp32 scale per stored head row: about half the cache bytes a decode step reads; bf16 / fp16 "
+                   "models on the GPU, any dtype on --device cpu). It composes with --weight-dtype, --decode-mma "
+                   "and --decode-graph")
     p.add_argument("--json", action="store_true", help="Print one JSON line instead of the text")
     return p
 
@@ -131,6 +140,9 @@ def main(argv=None) -> int:
         return _fail("--decode-mma has no MXFP4 kernels: drop it, or use --weight-dtype fp8 or model")
     if args.decode_mma and args.device == "cuda" and args.model_dtype not in ("bf16", "fp16"):
         return _fail(f"--decode-mma needs --model-dtype bf16 or fp16 on the GPU, got {args.model_dtype}")
+    if args.kv_dtype == "fp8" and args.device == "cuda" and args.model_dtype not in ("bf16", "fp16"):
+        return _fail(f"--kv-dtype fp8 needs --model-dtype bf16 or fp16 on the GPU (on --device cpu: any), "
+                     f"got {args.model_dtype}")
     if args.decode_mma and args.prompts_file is None and args.num_samples == 1:
         return _fail("--decode-mma applies to batched runs: give --num-samples above 1 or --prompts-file")
     if args.prompt_ids_file and args.prompts_file is None:
@@ -234,11 +246,11 @@ def main(argv=None) -> int:
             rows = generate_batch(model, prompts, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                                   key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
                                   graph=args.decode_graph, top_p=args.top_p, weights=weights,
-                                  mma=args.decode_mma)
+                                  mma=args.decode_mma, kv_dtype=args.kv_dtype)
         else:
             ids = generate(model, prompt, args.max_new_tokens, temperature=args.temperature, top_k=args.top_k,
                            key=key_from_seed(args.seed), eos_id=eos, step=args.sampler_step,
-                           graph=args.decode_graph, top_p=args.top_p, weights=weights)
+                           graph=args.decode_graph, top_p=args.top_p, weights=weights, kv_dtype=args.kv_dtype)
     except ValueError as e:
         return _fail(str(e))
     dt = time.perf_counter() - t0  # generate() returns host integers: the device work is finished

@@ -58,6 +58,16 @@ forms; it composes with ``weights`` and ``graph``). They keep the batch invarian
 depend on the batch it is in -- but add in another order than the one-row kernels, so the ids are those of
 ``generate_batch([prompt], mma=True)``, not bit for bit those of :func:`generate`; that is why the
 default is off. On the CPU the argument changes nothing; an fp32 or fp64 model on the GPU is refused.
+
+FP8 KV cache (``kv_dtype="fp8"`` of the caches, :class:`DecodeGraph`, :func:`generate` and
+:func:`generate_batch`): long batched decodes are bound by the cache bytes, so the cache can hold e4m3
+codes with one fp32 scale per stored head row (``utils/fp8.py``, a head row as its "row"): (D + 4) / 2D of
+the bytes. The two ops of a pass that touch the cache become their ``_kv8`` forms
+(``csrc/kernels/decode_kv8.hip``); :func:`prefill` computes the prompt's attention and the first token's
+logits on the unquantized K / V and stores their codes (``D.kv_quantize_prefill_``). K is quantized as the
+model-dtype cache would have held it, so a row appended by a decode step and a row written by the prefill
+follow one rule. It composes with ``weights``, ``mma`` and ``graph``; with ``kv_dtype="model"`` every path
+returns the bits it returned before. An fp32 or fp64 model on the GPU is refused.
 """
 from __future__ import annotations
 
@@ -71,21 +81,51 @@ from .ops import functional as Fx
 from .utils.sampling import token_key  # noqa: F401 - part of this module's interface
 
 
+KV_DTYPES = ("model", "fp8")
+
+
+def _check_kv_dtype(kv_dtype: str, device, dtype) -> None:
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be 'model' or 'fp8', got {kv_dtype!r}")
+    if kv_dtype == "fp8" and torch.device(device).type == "cuda" and dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"kv_dtype='fp8' needs a bf16 or fp16 model on the GPU (on the CPU: any dtype), got {dtype}")
+
+
+def _alloc_kv(cache, shape, device, dtype, kv_dtype: str) -> None:
+    """``k`` / ``v`` of ``shape`` [..., max_len, D] in ``dtype``, or, for ``kv_dtype == "fp8"``, as e4m3
+    codes (uint8) with the fp32 scales ``k_scale`` / ``v_scale`` of ``shape`` without D."""
+    _check_kv_dtype(kv_dtype, device, dtype)
+    fp8 = kv_dtype == "fp8"
+    cache.kv_dtype = kv_dtype
+    cache.k = torch.zeros(shape, dtype=torch.uint8 if fp8 else dtype, device=device)
+    cache.v = torch.zeros(shape, dtype=torch.uint8 if fp8 else dtype, device=device)
+    cache.k_scale = torch.zeros(shape[:-1], dtype=torch.float32, device=device) if fp8 else None
+    cache.v_scale = torch.zeros(shape[:-1], dtype=torch.float32, device=device) if fp8 else None
+
+
+def _kv_nbytes(cache) -> int:
+    return sum(t.numel() * t.element_size() for t in (cache.k, cache.v, cache.k_scale, cache.v_scale)
+               if t is not None)
+
+
 class KVCache:
     """Rotated K and V of the tokens seen so far: ``k`` / ``v`` ``[layers, Hkv, max_len, D]`` in the
     model dtype; ``length`` tokens are valid. ``max_len`` may not exceed ``model_args.seq_len``, the
-    length of the model's RoPE tables."""
+    length of the model's RoPE tables. ``kv_dtype="fp8"``: ``k`` / ``v`` hold e4m3 codes (uint8) and
+    ``k_scale`` / ``v_scale`` ``[layers, Hkv, max_len]`` one fp32 scale per stored head row
+    (``utils/fp8.py``); ``nbytes`` is what the cache takes either way."""
 
-    def __init__(self, model_args, max_len: int, device, dtype):
+    def __init__(self, model_args, max_len: int, device, dtype, kv_dtype: str = "model"):
         max_len = int(max_len)
         if max_len < 1 or max_len > model_args.seq_len:
             raise ValueError(f"KVCache: max_len {max_len} outside [1, {model_args.seq_len}] "
                              "(the model's sequence length, which sizes its RoPE tables)")
         shape = (model_args.n_layers, model_args.kv_heads, max_len, model_args.head_dim)
-        self.k = torch.zeros(shape, dtype=dtype, device=device)
-        self.v = torch.zeros(shape, dtype=dtype, device=device)
+        _alloc_kv(self, shape, device, dtype, kv_dtype)
         self.max_len = max_len
         self.length = 0
+
+    nbytes = property(_kv_nbytes)
 
 
 class _CacheRow:
@@ -96,6 +136,9 @@ class _CacheRow:
     def __init__(self, cache: "BatchKVCache", b: int):
         self._cache, self._b = cache, b
         self.k, self.v = cache.k[:, b], cache.v[:, b]
+        self.kv_dtype = cache.kv_dtype
+        self.k_scale = None if cache.k_scale is None else cache.k_scale[:, b]
+        self.v_scale = None if cache.v_scale is None else cache.v_scale[:, b]
         self.max_len = cache.max_len
 
     @property
@@ -115,7 +158,7 @@ class BatchKVCache:
     row ``b``, and ``steps`` counts the steps taken. ``row(b)`` is the row as a :class:`KVCache`, which
     :func:`prefill` fills."""
 
-    def __init__(self, model_args, batch: int, max_len: int, device, dtype):
+    def __init__(self, model_args, batch: int, max_len: int, device, dtype, kv_dtype: str = "model"):
         batch, max_len = int(batch), int(max_len)
         if batch < 1:
             raise ValueError(f"BatchKVCache: batch {batch} must be >= 1")
@@ -123,8 +166,7 @@ class BatchKVCache:
             raise ValueError(f"BatchKVCache: max_len {max_len} outside [1, {model_args.seq_len}] "
                              "(the model's sequence length, which sizes its RoPE tables)")
         shape = (model_args.n_layers, batch, model_args.kv_heads, max_len, model_args.head_dim)
-        self.k = torch.zeros(shape, dtype=dtype, device=device)
-        self.v = torch.zeros(shape, dtype=dtype, device=device)
+        _alloc_kv(self, shape, device, dtype, kv_dtype)
         self.batch, self.max_len = batch, max_len
         self.lengths = [0] * batch
         self.steps = 0
@@ -146,7 +188,12 @@ class BatchKVCache:
         n = self.lengths[src]
         self.k[:, dst, :, :n] = self.k[:, src, :, :n]
         self.v[:, dst, :, :n] = self.v[:, src, :, :n]
+        if self.kv_dtype == "fp8":
+            self.k_scale[:, dst, :, :n] = self.k_scale[:, src, :, :n]
+            self.v_scale[:, dst, :, :n] = self.v_scale[:, src, :, :n]
         self.set_length(dst, n)
+
+    nbytes = property(_kv_nbytes)
 
     def reset(self) -> None:
         """Every row empty again, for another batch of prompts. The tensors are kept and not cleared:
@@ -262,6 +309,11 @@ def _mv_swiglu_rows(x, w13, q, mma=False, mx4=False):
     return D.gemv_swiglu_rows(x, w13) if q is None else D.gemv_swiglu_rows_w8(x, q[0], q[1])
 
 
+def _kv8(cache, i: int):
+    """Layer i of an FP8 cache as the four operands of the ``_kv8`` ops."""
+    return cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i]
+
+
 def _check_mma(model, mma: bool, weights: Optional[Fp8Weights] = None) -> None:
     flat = model.flat
     if mma and isinstance(weights, Mxfp4Weights):
@@ -318,8 +370,12 @@ def prefill(model, tokens: Union[Sequence[int], torch.Tensor], cache: KVCache) -
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
         o, k, v = Fx.qkv_rope_attention_kv(xn, at.wqkv, cos, sin, P, hq, hkv, hd)
-        cache.k[i, :, :P] = k.reshape(P, hkv, hd).transpose(0, 1)
-        cache.v[i, :, :P] = v.reshape(P, hkv, hd).transpose(0, 1)
+        if cache.kv_dtype == "fp8":  # the prompt's own attention, above, ran on the unquantized K / V
+            D.kv_quantize_prefill_(k.reshape(P, hkv * hd), v.reshape(P, hkv * hd), cache.k[i], cache.v[i],
+                                   cache.k_scale[i], cache.v_scale[i])
+        else:
+            cache.k[i, :, :P] = k.reshape(P, hkv, hd).transpose(0, 1)
+            cache.v[i, :, :P] = v.reshape(P, hkv, hd).transpose(0, 1)
         da = Fx.linear(o.view(1, P, -1), at.wo.weight, None)
         h, hn = Fx.add_norm(h, da, layer.ffn_norm.weight, None, a.norm_eps, ln)
         d = Fx.feed_forward(hn, ff.w13, ff.w2.weight, None, None)
@@ -356,8 +412,12 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache,
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
         qkv = _mv(xn.reshape(-1), at.wqkv, qqkv, mx4)
-        D.qkv_append_(qkv, cos, sin, pos, cache.k[i], cache.v[i])
-        o = D.attn(qkv[: hq * hd], cache.k[i], cache.v[i], pos + 1)
+        if cache.kv_dtype == "fp8":
+            D.qkv_append_kv8_(qkv, cos, sin, pos, *_kv8(cache, i))
+            o = D.attn_kv8(qkv[: hq * hd], *_kv8(cache, i), pos + 1)
+        else:
+            D.qkv_append_(qkv, cos, sin, pos, cache.k[i], cache.v[i])
+            o = D.attn(qkv[: hq * hd], cache.k[i], cache.v[i], pos + 1)
         da = _mv(o, at.wo.weight, qo, mx4)
         h, hn = Fx.add_norm(h, da.view(1, -1), layer.ffn_norm.weight, None, a.norm_eps, ln)
         d = _mv(_mv_swiglu(hn.reshape(-1), ff.w13, q13, mx4), ff.w2.weight, q2, mx4).view(1, -1)
@@ -426,10 +486,16 @@ def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: B
     tok = torch.as_tensor(tokens, dtype=torch.int64).reshape(B, 1).to(dev)
     cos, sin = model.rope_cos, model.rope_sin
     pos0, lengths = cache.pos0, cache.lengths
-    logits = _rows_pass(
-        model, tok,
-        lambda i, qkv: D.qkv_append_rows_(qkv, cos, sin, pos0, t, cache.k[i], cache.v[i], lengths),
-        lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait, weights, mma)
+    if cache.kv_dtype == "fp8":
+        logits = _rows_pass(
+            model, tok,
+            lambda i, qkv: D.qkv_append_rows_kv8_(qkv, cos, sin, pos0, t, *_kv8(cache, i), lengths),
+            lambda i, q: D.attn_rows_kv8(q, *_kv8(cache, i), pos0, t, lengths), model._wait, weights, mma)
+    else:
+        logits = _rows_pass(
+            model, tok,
+            lambda i, qkv: D.qkv_append_rows_(qkv, cos, sin, pos0, t, cache.k[i], cache.v[i], lengths),
+            lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait, weights, mma)
     cache.steps = t + 1
     return logits
 
@@ -475,8 +541,10 @@ class DecodeGraph:
 
     EOS_CHECK_EVERY = 16  # tokens between two looks at the generated ids (one copy to the host each)
 
-    def __init__(self, model, batch: int, max_len: int, weights: Optional[Fp8Weights] = None, mma: bool = False):
+    def __init__(self, model, batch: int, max_len: int, weights: Optional[Fp8Weights] = None, mma: bool = False,
+                 kv_dtype: str = "model"):
         flat, a = model.flat, model.model_args
+        _check_kv_dtype(kv_dtype, flat.device, flat.dtype)
         _check_weights(model, weights)
         _check_mma(model, mma, weights)
         if mma and int(batch) > MAX_BATCH:
@@ -489,7 +557,7 @@ class DecodeGraph:
         self.model = model
         self.weights = weights
         self.mma = bool(mma)
-        self.cache = BatchKVCache(a, batch, max_len, dev, flat.dtype)
+        self.cache = BatchKVCache(a, batch, max_len, dev, flat.dtype, kv_dtype=kv_dtype)
         self.batch, self.max_len = self.cache.batch, self.cache.max_len
         B = self.batch
         self.tok = torch.zeros(B, 1, dtype=torch.int64, device=dev)
@@ -517,11 +585,18 @@ class DecodeGraph:
         model, cache, ctl, pos0 = self.model, self.cache, self.ctl, self.pos0
         cos, sin = model.rope_cos, model.rope_sin
         D.sample_dev_(self.logits, ctl, self.tok, self.out)
-        logits = _rows_pass(
-            model, self.tok,
-            lambda i, qkv: D.qkv_append_rows_dev_(qkv, cos, sin, pos0, ctl, cache.k[i], cache.v[i]),
-            lambda i, q: D.attn_rows_dev(q, cache.k[i], cache.v[i], pos0, ctl, self.part, self.o), None,
-            self.weights, self.mma)
+        if cache.kv_dtype == "fp8":
+            logits = _rows_pass(
+                model, self.tok,
+                lambda i, qkv: D.qkv_append_rows_dev_kv8_(qkv, cos, sin, pos0, ctl, *_kv8(cache, i)),
+                lambda i, q: D.attn_rows_dev_kv8(q, *_kv8(cache, i), pos0, ctl, self.part, self.o), None,
+                self.weights, self.mma)
+        else:
+            logits = _rows_pass(
+                model, self.tok,
+                lambda i, qkv: D.qkv_append_rows_dev_(qkv, cos, sin, pos0, ctl, cache.k[i], cache.v[i]),
+                lambda i, q: D.attn_rows_dev(q, cache.k[i], cache.v[i], pos0, ctl, self.part, self.o), None,
+                self.weights, self.mma)
         self.logits.copy_(logits)
         D.ctl_advance_(ctl)
 
@@ -624,7 +699,8 @@ MAX_BATCH = 64
 def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0,
                    top_k: int = 0, key: int = 0, eos_id: Optional[int] = None, step: int = 0,
                    graph: bool = False, top_p: float = 1.0,
-                   weights: Optional[Fp8Weights] = None, mma: bool = False) -> List[List[int]]:
+                   weights: Optional[Fp8Weights] = None, mma: bool = False,
+                   kv_dtype: str = "model") -> List[List[int]]:
     """:func:`generate` for B prompts at once: the ids generated after each of ``prompts``. New token
     ``t`` of every row comes from one ``D.sample(logits[B, V], ..., token_key(key, t), step)``, row
     ``b``'s draw being the sampler's row ``b``: row 0 equals ``generate`` with the same arguments, and
@@ -635,9 +711,11 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     capture). ``weights``: decode with these FP8 weights (the prompts' K/V and the first token's logits
     come from the prefill, on the unquantized weights). ``mma``: the decode products on the matrix-core
     kernels: a row's ids still do not depend on its batch, but they are those of
-    ``generate_batch([prompt], ..., mma=True)``, not bit for bit those of :func:`generate`."""
+    ``generate_batch([prompt], ..., mma=True)``, not bit for bit those of :func:`generate`. ``kv_dtype="fp8"``:
+    the cache holds e4m3 codes with one scale per head row (:class:`KVCache`); it composes with the rest."""
     _check_weights(model, weights)
     _check_mma(model, mma, weights)
+    _check_kv_dtype(kv_dtype, model.flat.device, model.flat.dtype)
     rows = [[int(t) for t in p] for p in prompts]
     n_new = int(max_new_tokens)
     a = model.model_args
@@ -650,9 +728,9 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
         return [[] for _ in rows]
     flat = model.flat
     if graph and graph_supported(model):
-        return DecodeGraph(model, B, max(len(p) for p in rows) + n_new, weights, mma).run(
+        return DecodeGraph(model, B, max(len(p) for p in rows) + n_new, weights, mma, kv_dtype).run(
             rows, n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id, top_p=top_p)
-    cache = BatchKVCache(a, B, max(len(p) for p in rows) + n_new, flat.device, flat.dtype)
+    cache = BatchKVCache(a, B, max(len(p) for p in rows) + n_new, flat.device, flat.dtype, kv_dtype=kv_dtype)
     logits = _prefill_rows(model, rows, cache)
     out: List[List[int]] = [[] for _ in rows]
     live = [True] * B
@@ -671,14 +749,16 @@ def generate_batch(model, prompts: Sequence[Sequence[int]], max_new_tokens: int,
 @torch.no_grad()
 def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
              key: int = 0, eos_id: Optional[int] = None, step: int = 0, graph: bool = False,
-             top_p: float = 1.0, weights: Optional[Fp8Weights] = None) -> List[int]:
+             top_p: float = 1.0, weights: Optional[Fp8Weights] = None, kv_dtype: str = "model") -> List[int]:
     """The ids generated after ``prompt_ids`` (at most ``max_new_tokens``; ends after ``eos_id``,
     which is included). ``temperature == 0`` is greedy; otherwise temperature / top-k / top-p sampling
     (``top_p`` in (0, 1], 1: off) with the stateless sampler under ``(key, step)``. ``graph=True`` decodes with a one-row
     :class:`DecodeGraph` (the multi-row kernels at B = 1 return the one-row kernels' bits). ``weights``:
     decode with these FP8 weights (:class:`Fp8Weights`); the prompt's K/V and the first token's logits
-    come from the prefill, on the unquantized weights."""
+    come from the prefill, on the unquantized weights. ``kv_dtype="fp8"``: an FP8 cache (:class:`KVCache`);
+    the prompt's own attention and the first token's logits still come from the unquantized K and V."""
     _check_weights(model, weights)
+    _check_kv_dtype(kv_dtype, model.flat.device, model.flat.dtype)
     prompt = [int(t) for t in prompt_ids]
     n_new = int(max_new_tokens)
     a = model.model_args
@@ -694,10 +774,10 @@ def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature:
         return []
     flat = model.flat
     if graph and graph_supported(model):
-        return DecodeGraph(model, 1, len(prompt) + n_new, weights).run(
+        return DecodeGraph(model, 1, len(prompt) + n_new, weights, kv_dtype=kv_dtype).run(
             [prompt], n_new, temperature=temperature, top_k=top_k, key=key, step=step, eos_id=eos_id,
             top_p=top_p)[0]
-    cache = KVCache(a, len(prompt) + n_new, flat.device, flat.dtype)
+    cache = KVCache(a, len(prompt) + n_new, flat.device, flat.dtype, kv_dtype=kv_dtype)
     logits = prefill(model, prompt, cache)
     out: List[int] = []
     for t in range(n_new):

@@ -424,3 +424,130 @@ def sample_dev_(logits: torch.Tensor, ctl: torch.Tensor, tok: torch.Tensor, out:
     tok.copy_(nxt.view_as(tok))
     if 0 <= t < out.shape[1]:
         out[:, t] = nxt
+
+
+# ---------------------------------------------------------------------------------------------
+# The FP8 KV cache forms (csrc/kernels/decode_kv8.hip): a cache is e4m3 codes (uint8, the shape of the
+# model-dtype cache) with one fp32 scale per stored head row (the cache's shape without D), in the format
+# of ``utils.fp8`` with one head row -- the D values of K or V of one (sequence, kv head, position) -- as a
+# "row" of its ``quantize_rows``. K is quantized as the model-dtype cache would have stored it: rotated and
+# rounded to the activation's dtype. The route is chosen as for the ``_w8`` ops, by device and dtype alone:
+# bf16 / fp16 GPU tensors run the kernels and an operand they cannot take is an error of the op's host
+# checks; fp32 and fp64 tensors on the GPU raise here; CPU tensors take the composed definition, which is
+# ``utils.fp8.quantize_rows`` behind the model-dtype append, and ``utils.fp8.dequant`` in front of ``attn``.
+# ---------------------------------------------------------------------------------------------
+def _kv8_native(op: str, x: torch.Tensor) -> bool:
+    if not x.is_cuda:
+        return False
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        raise ValueError(f"{op}: the FP8 KV cache kernels take bf16 or fp16 activations on the GPU, got {x.dtype}")
+    return True
+
+
+def _kv8_store(rows: torch.Tensor, codes: torch.Tensor, scale: torch.Tensor) -> None:
+    """Head rows ``rows [..., D]`` into ``codes [..., D]`` / ``scale [...]`` (views of a cache), by the
+    definition."""
+    from ..utils.fp8 import quantize_rows as definition
+
+    c, s = definition(rows.reshape(-1, rows.shape[-1]))
+    codes.copy_(c.view(codes.shape))
+    scale.copy_(s.view(scale.shape))
+
+
+def _kv8_values(codes: torch.Tensor, scale: torch.Tensor, n: int, dtype) -> torch.Tensor:
+    """``code * scale`` of keys ``0 .. n - 1`` of a cache [Hkv, Smax, D], in ``dtype``."""
+    from ..utils.fp8 import dequant
+
+    c = codes[:, :n]
+    return dequant(c.reshape(-1, c.shape[-1]), scale[:, :n].reshape(-1)).view(c.shape).to(dtype)
+
+
+def kv_quantize_prefill_(k: torch.Tensor, v: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                         k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+    """The rotated K and the V of a prompt, ``[P, Hkv D]`` each, into positions ``0 .. P - 1`` of one layer
+    of one sequence: codes [Hkv, Smax, D], scales [Hkv, Smax]."""
+    if _kv8_native("kv_quantize_prefill_", k):
+        kernels().kv_quantize_prefill_(k, v, k_codes, v_codes, k_scale, v_scale)
+        return
+    hkv, _, d = k_codes.shape
+    P = k.shape[0]
+    _kv8_store(k.view(P, hkv, d).transpose(0, 1), k_codes[:, :P], k_scale[:, :P])
+    _kv8_store(v.view(P, hkv, d).transpose(0, 1), v_codes[:, :P], v_scale[:, :P])
+
+
+def qkv_append_kv8_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: int, k_codes: torch.Tensor,
+                    v_codes: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+    """``qkv_append_`` into an FP8 cache: Q rotated in place; the rotated K (in qkv's dtype) and V
+    quantized into ``*_codes[:, pos]`` / ``*_scale[:, pos]``."""
+    if _kv8_native("qkv_append_kv8_", qkv):
+        kernels().decode_qkv_append_kv8_(qkv, cos, sin, int(pos), k_codes, v_codes, k_scale, v_scale)
+        return
+    hkv, smax, d = k_codes.shape
+    if not 0 <= pos < smax:
+        raise ValueError(f"qkv_append_kv8_: pos {pos} outside the cache [0, {smax})")
+    kv = qkv.new_empty(2, hkv, 1, d)  # a one-position model-dtype cache, filled by the definition
+    qkv_append_(qkv, cos[pos : pos + 1], sin[pos : pos + 1], 0, kv[0], kv[1])
+    _kv8_store(kv[0, :, 0], k_codes[:, pos], k_scale[:, pos])
+    _kv8_store(kv[1, :, 0], v_codes[:, pos], v_scale[:, pos])
+
+
+def attn_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_scale: torch.Tensor,
+             v_scale: torch.Tensor, n_keys: int) -> torch.Tensor:
+    """``attn`` over ``code * scale`` of keys ``0 .. n_keys - 1`` of an FP8 cache."""
+    if _kv8_native("attn_kv8", q):
+        return kernels().decode_attn_kv8(q, k_codes, v_codes, k_scale, v_scale, int(n_keys))
+    n = int(n_keys)
+    if not 1 <= n <= k_codes.shape[1]:
+        raise ValueError(f"attn_kv8: n_keys {n} outside [1, Smax = {k_codes.shape[1]}]")
+    return attn(q, _kv8_values(k_codes, k_scale, n, q.dtype), _kv8_values(v_codes, v_scale, n, q.dtype), n)
+
+
+def qkv_append_rows_kv8_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor, t: int,
+                         k_codes: torch.Tensor, v_codes: torch.Tensor, k_scale: torch.Tensor,
+                         v_scale: torch.Tensor, positions: Sequence[int]) -> None:
+    """``qkv_append_kv8_`` on row b of qkv at position ``pos0[b] + t`` of caches [B, Hkv, Smax, D]
+    (``positions``: the host's copy of ``pos0``, as for ``qkv_append_rows_``)."""
+    if _kv8_native("qkv_append_rows_kv8_", qkv):
+        kernels().decode_qkv_append_rows_kv8_(qkv, cos, sin, pos0, int(t), max(positions) + int(t), k_codes,
+                                              v_codes, k_scale, v_scale)
+        return
+    for b, p in enumerate(positions):
+        qkv_append_kv8_(qkv[b], cos, sin, int(p) + int(t), k_codes[b], v_codes[b], k_scale[b], v_scale[b])
+
+
+def attn_rows_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_scale: torch.Tensor,
+                  v_scale: torch.Tensor, pos0: torch.Tensor, t: int, positions: Sequence[int]) -> torch.Tensor:
+    """o[B, Hq D]; row b equals ``attn_kv8`` of q[b] over its ``pos0[b] + t + 1`` keys."""
+    if _kv8_native("attn_rows_kv8", q):
+        return kernels().decode_attn_rows_kv8(q, k_codes, v_codes, k_scale, v_scale, pos0, int(t),
+                                              max(positions) + int(t) + 1)
+    return torch.stack([attn_kv8(q[b], k_codes[b], v_codes[b], k_scale[b], v_scale[b], int(p) + int(t) + 1)
+                        for b, p in enumerate(positions)])
+
+
+def qkv_append_rows_dev_kv8_(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos0: torch.Tensor,
+                             ctl: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor,
+                             k_scale: torch.Tensor, v_scale: torch.Tensor) -> None:
+    """``qkv_append_rows_kv8_`` with ``t`` taken from ``ctl``; a position outside the cache or the RoPE
+    tables writes nothing."""
+    if _kv8_native("qkv_append_rows_dev_kv8_", qkv):
+        kernels().decode_qkv_append_rows_dev_kv8_(qkv, cos, sin, pos0, ctl, k_codes, v_codes, k_scale, v_scale)
+        return
+    t = read_ctl(ctl)[0]
+    limit = min(k_codes.shape[2], cos.shape[0])
+    for b, p in enumerate(pos0.tolist()):
+        if 0 <= p + t < limit:
+            qkv_append_kv8_(qkv[b], cos, sin, p + t, k_codes[b], v_codes[b], k_scale[b], v_scale[b])
+
+
+def attn_rows_dev_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_scale: torch.Tensor,
+                      v_scale: torch.Tensor, pos0: torch.Tensor, ctl: torch.Tensor, part: torch.Tensor,
+                      o: torch.Tensor) -> torch.Tensor:
+    """``attn_rows_kv8`` with ``t`` taken from ``ctl``, into the caller's ``o``; ``part`` as for
+    ``attn_rows_dev``. Returns ``o``."""
+    if _kv8_native("attn_rows_dev_kv8", q):
+        kernels().decode_attn_rows_dev_kv8(q, k_codes, v_codes, k_scale, v_scale, pos0, ctl, part, o)
+        return o
+    t = read_ctl(ctl)[0]
+    o.copy_(attn_rows_kv8(q, k_codes, v_codes, k_scale, v_scale, pos0, t, pos0.tolist()))
+    return o
