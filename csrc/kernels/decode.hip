@@ -33,12 +33,16 @@
 // right for any token of any call (generation.DecodeGraph). They run the same per-row code and
 // return the same bits. decode_ctl_advance_ steps the counter in a launch of its own, after every
 // reader of the pass.
-#include <climits>
+//
+// Host side: the operand checks and the head_dim / GQA / row-tile dispatch are decode_host.h's, shared
+// with the other decode files; the host-step and the device-step form of a `_rows` cache op are one
+// function that takes the control block or a null pointer (append_rows, attn_rows_into), as in
+// decode_kv8.hip.
 #include <type_traits>
 
-#include "decode_attn.h"  // LOG2E, DECODE_CHUNK, CTL_*, row_keys, the merge kernels (shared with decode_kv8.hip)
+#include "decode_host.h"  // the operand checks and dispatch macros; decode_attn.h: LOG2E, DECODE_CHUNK, CTL_*,
+                          // row_keys, rope8, the merge kernels (shared with decode_kv8.hip)
 #include "sround.h"
-#include "torch_utils.h"
 
 namespace {
 
@@ -231,16 +235,9 @@ __device__ __forceinline__ void qkv_append_vec(int i, typename E::T* __restrict_
   float x[8];
   ld8<E>(qkv + col, x);
   if (head < hq + hkv) {
-    const float4 c = *reinterpret_cast<const float4*>(cos_row + (within >> 1));
-    const float4 s = *reinterpret_cast<const float4*>(sin_row + (within >> 1));
-    const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {s.x, s.y, s.z, s.w};
     float r[8];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const float a = x[2 * p], b = x[2 * p + 1];
-      r[2 * p] = a * cc[p] - b * ss[p];
-      r[2 * p + 1] = a * ss[p] + b * cc[p];
-    }
+    rope8(x, *reinterpret_cast<const float4*>(cos_row + (within >> 1)),
+          *reinterpret_cast<const float4*>(sin_row + (within >> 1)), r);
     if (head < hq) st8<E>(qkv + col, r);
     else st8<E>(kc + ((long)(head - hq) * smax + pos) * d + within, r);
   } else {
@@ -862,257 +859,276 @@ __global__ void ctl_advance_kernel(int* __restrict__ ctl) {
   if (blockIdx.x == 0 && threadIdx.x == 0) ctl[CTL_T] = ctl[CTL_T] + 1;
 }
 
-void check_vec(const char* op, const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
-}
-
-template <bool SWIGLU>
-at::Tensor gemv_impl(const char* op, const at::Tensor& x, const at::Tensor& w,
-                     const c10::optional<at::Tensor>& residual) {
-  FT_CHECK_MODEL_DTYPE(w);
-  check_vec(op, x, "x");
-  check_vec(op, w, "w");
-  TORCH_CHECK(x.scalar_type() == w.scalar_type() && x.device() == w.device(), op, ": x / w dtype or device mismatch");
-  TORCH_CHECK(w.dim() == 2 && x.dim() == 1 && x.size(0) == w.size(1), op, ": x [K], w [N, K]");
-  const int64_t rows = w.size(0), K = w.size(1);
-  const int vn = w.scalar_type() == at::kFloat ? 4 : 8;
-  TORCH_CHECK(K > 0 && K % vn == 0, op, ": K must be a positive multiple of ", vn, " (16-byte row vectors)");
-  TORCH_CHECK(rows > 0 && rows <= INT_MAX && K <= INT_MAX, op, ": N and K must fit 32 bits");
-  TORCH_CHECK(!SWIGLU || rows % 2 == 0, op, ": w13 must be [2H, K]");
-  const int64_t N = SWIGLU ? rows / 2 : rows;
-  const bool has_res = residual.has_value() && residual->defined();
-  if (has_res) {
-    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() && residual->scalar_type() == w.scalar_type() &&
-                    residual->device() == w.device() && residual->numel() == N,
-                op, ": residual must be a contiguous [N] tensor of w's dtype and device");
-  }
-  const at::DeviceGuard guard(w.device());
-  auto y = at::empty({N}, w.options());
-  FT_DISPATCH_E(w.scalar_type(),
-                hipLaunchKernelGGL((gemv_kernel<E, SWIGLU>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, ft_stream(),
-                                   cptr<typename E::T>(x), cptr<typename E::T>(w),
-                                   has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y),
-                                   (int)N, (int)K));
-  FT_LAUNCH_CHECK();
-  return y;
-}
-
 // The tile heights of gemv_rows_kernel. R <= 8 takes the smallest tile that holds it; above, tiles
 // of GEMV_ROWS_TILE (SWIGLU: GEMV_SWIGLU_ROWS_TILE) rows.
 constexpr int GEMV_ROWS_TILE = 8;
 constexpr int GEMV_SWIGLU_ROWS_TILE = 8;
 
+// x [K] (rows == false) or [R, K]; the result is [N] or [R, N].
 template <bool SWIGLU>
-at::Tensor gemv_rows_impl(const char* op, const at::Tensor& x, const at::Tensor& w,
-                          const c10::optional<at::Tensor>& residual) {
+at::Tensor gemv_impl(const char* op, bool rows, const at::Tensor& x, const at::Tensor& w,
+                     const c10::optional<at::Tensor>& residual) {
   FT_CHECK_MODEL_DTYPE(w);
   check_vec(op, x, "x");
   check_vec(op, w, "w");
   TORCH_CHECK(x.scalar_type() == w.scalar_type() && x.device() == w.device(), op, ": x / w dtype or device mismatch");
-  TORCH_CHECK(w.dim() == 2 && x.dim() == 2 && x.size(1) == w.size(1), op, ": x [R, K], w [N, K]");
-  const int64_t R = x.size(0), rows = w.size(0), K = w.size(1);
+  TORCH_CHECK(w.dim() == 2 && x.dim() == (rows ? 2 : 1) && x.size(-1) == w.size(1), op,
+              rows ? ": x [R, K], w [N, K]" : ": x [K], w [N, K]");
+  const int64_t R = rows ? x.size(0) : 1, nrows = w.size(0), K = w.size(1);
   const int vn = w.scalar_type() == at::kFloat ? 4 : 8;
   TORCH_CHECK(K > 0 && K % vn == 0, op, ": K must be a positive multiple of ", vn, " (16-byte row vectors)");
   TORCH_CHECK(R >= 1 && R <= INT_MAX, op, ": x needs at least one row");
-  TORCH_CHECK(rows > 0 && rows <= INT_MAX && K <= INT_MAX, op, ": N and K must fit 32 bits");
-  TORCH_CHECK(!SWIGLU || rows % 2 == 0, op, ": w13 must be [2H, K]");
-  const int64_t N = SWIGLU ? rows / 2 : rows;
+  TORCH_CHECK(nrows > 0 && nrows <= INT_MAX && K <= INT_MAX, op, ": N and K must fit 32 bits");
+  TORCH_CHECK(!SWIGLU || nrows % 2 == 0, op, ": w13 must be [2H, K]");
+  const int64_t N = SWIGLU ? nrows / 2 : nrows;
   const bool has_res = residual.has_value() && residual->defined();
-  if (has_res) {
-    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() && residual->scalar_type() == w.scalar_type() &&
-                    residual->device() == w.device() && residual->dim() == 2 && residual->size(0) == R &&
-                    residual->size(1) == N,
-                op, ": residual must be a contiguous [R, N] tensor of w's dtype and device");
-  }
+  if (has_res) check_residual(op, *residual, x, N);
   constexpr int TOP = SWIGLU ? GEMV_SWIGLU_ROWS_TILE : GEMV_ROWS_TILE;
-  const int rt = R == 1 ? 1 : R == 2 ? 2 : (R <= 4 || TOP == 4) ? 4 : 8;
+  const int rt = rows_tile(R, TOP);
   const int64_t ntiles = (R + rt - 1) / rt;
   const int64_t blocks = (N + 3) / 4 * ntiles;
   TORCH_CHECK(blocks <= INT_MAX, op, ": too many workgroups (N / 4 x row tiles)");
   const at::DeviceGuard guard(w.device());
-  auto y = at::empty({R, N}, w.options());
-#define FT_GEMV_ROWS(RT)                                                                                       \
-  hipLaunchKernelGGL((gemv_rows_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(256), 0, ft_stream(),     \
-                     cptr<typename E::T>(x), cptr<typename E::T>(w),                                           \
-                     has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y), (int)N, (int)K, \
-                     (int)R, (int)ntiles)
+  auto y = rows ? at::empty({R, N}, w.options()) : at::empty({N}, w.options());
   FT_DISPATCH_E(w.scalar_type(), {
-    if (rt == 1) FT_GEMV_ROWS(1);
-    else if (rt == 2) FT_GEMV_ROWS(2);
-    else if (rt == 4) FT_GEMV_ROWS(4);
-    else FT_GEMV_ROWS(TOP);
+    typedef typename E::T T;
+    const T* res = has_res ? cptr<T>(*residual) : nullptr;
+    if (!rows)
+      hipLaunchKernelGGL((gemv_kernel<E, SWIGLU>), dim3((unsigned)blocks), dim3(256), 0, ft_stream(), cptr<T>(x),
+                         cptr<T>(w), res, mptr<T>(y), (int)N, (int)K);
+    else
+      FT_ROWS_TILE(rt, TOP, {
+        hipLaunchKernelGGL((gemv_rows_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(256), 0, ft_stream(),
+                           cptr<T>(x), cptr<T>(w), res, mptr<T>(y), (int)N, (int)K, (int)R, (int)ntiles);
+      });
   });
-#undef FT_GEMV_ROWS
   FT_LAUNCH_CHECK();
   return y;
 }
 
-void check_cache(const char* op, const at::Tensor& c, const at::Tensor& like, int64_t hkv, int64_t d) {
-  TORCH_CHECK(c.is_cuda() && c.device() == like.device() && c.scalar_type() == like.scalar_type(), op,
-              ": the caches must be on qkv's device, in its dtype");
-  TORCH_CHECK(c.is_contiguous() && c.dim() == 3 && c.size(0) == hkv && c.size(2) == d, op,
-              ": a cache is a contiguous [Hkv, Smax, D] tensor");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(c.data_ptr()) % 16 == 0, op, ": a cache must be 16-byte aligned");
-}
-
-template <class E, int D>
-void launch_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& part,
-                 const at::Tensor& o, int hq, int hkv, int n_keys, int nchunks) {
-  const int G = hq / hkv;
-  const dim3 grid(hkv, nchunks);
-  const float scale = 1.f / sqrtf((float)D);
-  const long smax = kc.size(1);
-#define FT_ATTN(GT)                                                                                        \
-  hipLaunchKernelGGL((decode_attn_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(), cptr<typename E::T>(q), \
-                     cptr<typename E::T>(kc), cptr<typename E::T>(vc), mptr<float>(part), hq, hkv, smax, n_keys, scale)
-  if (G == 1) FT_ATTN(1);
-  else if (G == 2) FT_ATTN(2);
-  else if (G <= 4) FT_ATTN(4);
-  else FT_ATTN(8);
-#undef FT_ATTN
-  FT_LAUNCH_CHECK();
-  hipLaunchKernelGGL((decode_attn_merge_kernel<E, D>), dim3(hq), dim3(D), 0, ft_stream(), cptr<float>(part),
-                     mptr<typename E::T>(o), hq, nchunks);
-}
-
-template <class E, int D>
-void launch_attn_rows(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& part,
-                      const at::Tensor& o, const at::Tensor& pos0, int t, int max_keys, int max_chunks, int B,
-                      int hq, int hkv) {
-  const int G = hq / hkv;
-  const dim3 grid(hkv, max_chunks, B);
-  const float scale = 1.f / sqrtf((float)D);
-  const long smax = kc.size(2);
-#define FT_ATTN(GT)                                                                                             \
-  hipLaunchKernelGGL((decode_attn_rows_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(), cptr<typename E::T>(q), \
-                     cptr<typename E::T>(kc), cptr<typename E::T>(vc), mptr<float>(part), cptr<int>(pos0), t,   \
-                     max_keys, (long)q.stride(0), hq, hkv, smax, scale)
-  if (G == 1) FT_ATTN(1);
-  else if (G == 2) FT_ATTN(2);
-  else if (G <= 4) FT_ATTN(4);
-  else FT_ATTN(8);
-#undef FT_ATTN
-  FT_LAUNCH_CHECK();
-  hipLaunchKernelGGL((decode_attn_merge_rows_kernel<E, D>), dim3(hq, B), dim3(D), 0, ft_stream(), cptr<float>(part),
-                     mptr<typename E::T>(o), cptr<int>(pos0), t, max_keys, max_chunks, hq);
-}
-
-template <class E, int D>
-void launch_attn_rows_dev(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& part,
-                          const at::Tensor& o, const at::Tensor& pos0, const at::Tensor& ctl, int max_chunks, int B,
-                          int hq, int hkv) {
-  const int G = hq / hkv;
-  const dim3 grid(hkv, max_chunks, B);
-  const float scale = 1.f / sqrtf((float)D);
-  const long smax = kc.size(2);
-#define FT_ATTN(GT)                                                                                       \
-  hipLaunchKernelGGL((decode_attn_rows_dev_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),            \
-                     cptr<typename E::T>(q), cptr<typename E::T>(kc), cptr<typename E::T>(vc), mptr<float>(part), \
-                     cptr<int>(pos0), cptr<int>(ctl), (long)q.stride(0), hq, hkv, smax, scale)
-  if (G == 1) FT_ATTN(1);
-  else if (G == 2) FT_ATTN(2);
-  else if (G <= 4) FT_ATTN(4);
-  else FT_ATTN(8);
-#undef FT_ATTN
-  FT_LAUNCH_CHECK();
-  hipLaunchKernelGGL((decode_attn_merge_rows_dev_kernel<E, D>), dim3(hq, B), dim3(D), 0, ft_stream(),
-                     cptr<float>(part), mptr<typename E::T>(o), cptr<int>(pos0), cptr<int>(ctl), (int)smax, max_chunks,
-                     hq);
-}
-
-// The operands the two batched cache ops share: caches [B, Hkv, Smax, D] of x's dtype, pos0 int32 [B].
-void check_rows(const char* op, const at::Tensor& x, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                const at::Tensor& pos0) {
+// check_kv of decode_host.h for caches of the activation's own dtype. The appends take any head_dim of
+// whole 8-column vectors; attention (attn == true) has kernels for 64 and 128.
+KvShape check_kvm(const char* op, const at::Tensor& x, const at::Tensor& kc, const at::Tensor& vc, bool rows,
+                  bool attn) {
   FT_CHECK_MODEL_DTYPE(x);
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.size(0) >= 1, op, ": the activation is a GPU tensor [B, width], B >= 1");
-  TORCH_CHECK(x.stride(1) == 1 && x.stride(0) >= x.size(1) && x.stride(0) % 8 == 0 &&
-                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              op, ": the activation's rows must be dense, 16-byte aligned, a multiple of 8 elements apart");
-  TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(0) == x.size(0), op, ": a cache is [B, Hkv, Smax, D]");
-  for (const at::Tensor* c : {&k_cache, &v_cache}) {
-    TORCH_CHECK(c->is_cuda() && c->device() == x.device() && c->scalar_type() == x.scalar_type(), op,
-                ": the caches must be on the activation's device, in its dtype");
-    TORCH_CHECK(c->is_contiguous() && c->sizes() == k_cache.sizes(), op,
-                ": the caches are contiguous [B, Hkv, Smax, D] tensors of one shape");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": a cache must be 16-byte aligned");
-  }
-  TORCH_CHECK(pos0.is_cuda() && pos0.device() == x.device() && pos0.scalar_type() == at::kInt &&
-                  pos0.is_contiguous() && pos0.dim() == 1 && pos0.size(0) == x.size(0),
-              op, ": pos0 must be a contiguous int32 [B] tensor on the activation's device");
-  TORCH_CHECK(x.size(0) <= 65535 && k_cache.size(2) <= INT_MAX, op, ": B or Smax too large");
+  const KvShape s = check_kv(op, x, kc, vc, x.scalar_type(), rows);
+  TORCH_CHECK(attn ? s.d == 64 || s.d == 128 : s.d > 0 && s.d % 8 == 0, op,
+              attn ? ": head_dim must be 64 or 128" : ": head_dim must be a multiple of 8");
+  return s;
 }
 
-void check_ctl(const char* op, const at::Tensor& ctl, const at::Tensor& like) {
-  TORCH_CHECK(ctl.is_cuda() && ctl.device() == like.device() && ctl.scalar_type() == at::kInt && ctl.is_contiguous() &&
-                  ctl.dim() == 1 && ctl.size(0) >= CTL_WORDS,
-              op, ": ctl must be a contiguous int32 tensor of at least ", (int)CTL_WORDS, " words on the operands' device");
+// t from the host (ctl == nullptr; the positions are checked up to max_pos) or from ctl[CTL_T] (the
+// bound is the capacity of the cache and the RoPE tables: the caller checks its own count of steps).
+void append_rows(const char* op, const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
+                 const at::Tensor& pos0, const at::Tensor* ctl, int64_t t, int64_t max_pos, const at::Tensor& kc,
+                 const at::Tensor& vc) {
+  const KvShape s = check_kvm(op, qkv, kc, vc, true, false);
+  check_pos0(op, pos0, qkv);
+  TORCH_CHECK(qkv.is_contiguous(), op, ": qkv must be contiguous");
+  const int64_t B = qkv.size(0), hq = qkv_heads(op, qkv.size(1), s);
+  const long limit = check_append_rows(op, qkv, cos_t, sin_t, ctl, t, max_pos, s);
+  const at::DeviceGuard guard(qkv.device());
+  const int nvec = (int)(qkv.size(1) / 8);
+  const dim3 grid((nvec + 255) / 256, (unsigned)B);
+  FT_DISPATCH_E(qkv.scalar_type(), {
+    typedef typename E::T T;
+    if (ctl != nullptr)
+      hipLaunchKernelGGL(qkv_append_rows_dev_kernel<E>, grid, dim3(256), 0, ft_stream(), mptr<T>(qkv),
+                         cptr<float>(cos_t), cptr<float>(sin_t), cptr<int>(pos0), cptr<int>(*ctl), mptr<T>(kc),
+                         mptr<T>(vc), (int)hq, (int)s.hkv, (int)s.d, (long)s.smax, limit);
+    else
+      hipLaunchKernelGGL(qkv_append_rows_kernel<E>, grid, dim3(256), 0, ft_stream(), mptr<T>(qkv),
+                         cptr<float>(cos_t), cptr<float>(sin_t), cptr<int>(pos0), (int)t, mptr<T>(kc), mptr<T>(vc),
+                         (int)hq, (int)s.hkv, (int)s.d, (long)s.smax, limit);
+  });
+  FT_LAUNCH_CHECK();
+}
+
+// The rows forms into the caller's part [B, max_chunks, Hq, D + 2] and o [B, Hq D]; t from the host
+// (ctl == nullptr, the grid over max_keys) or from ctl[CTL_T] (the grid over the capacity: a row's merge
+// folds the chunks its key count min(pos0[b] + t + 1, Smax) needs, the bits of decode_attn_rows).
+void attn_rows_into(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos0,
+                    const at::Tensor* ctl, int t, int max_keys, int max_chunks, const KvShape& s, int64_t hq,
+                    const at::Tensor& part, const at::Tensor& o) {
+  const int B = (int)q.size(0), G = (int)(hq / s.hkv);
+  const dim3 grid((unsigned)s.hkv, max_chunks, B);
+  FT_DISPATCH_E(q.scalar_type(), FT_DECODE_D(s.d, {
+    typedef typename E::T T;
+    const float scale = 1.f / sqrtf((float)D);
+    if (ctl != nullptr) {
+      FT_DECODE_GT(G, hipLaunchKernelGGL((decode_attn_rows_dev_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),
+                                         cptr<T>(q), cptr<T>(kc), cptr<T>(vc), mptr<float>(part), cptr<int>(pos0),
+                                         cptr<int>(*ctl), (long)q.stride(0), (int)hq, (int)s.hkv, (long)s.smax,
+                                         scale));
+      FT_LAUNCH_CHECK();
+      hipLaunchKernelGGL((decode_attn_merge_rows_dev_kernel<E, D>), dim3((unsigned)hq, B), dim3(D), 0, ft_stream(),
+                         cptr<float>(part), mptr<T>(o), cptr<int>(pos0), cptr<int>(*ctl), (int)s.smax, max_chunks,
+                         (int)hq);
+    } else {
+      FT_DECODE_GT(G, hipLaunchKernelGGL((decode_attn_rows_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),
+                                         cptr<T>(q), cptr<T>(kc), cptr<T>(vc), mptr<float>(part), cptr<int>(pos0), t,
+                                         max_keys, (long)q.stride(0), (int)hq, (int)s.hkv, (long)s.smax, scale));
+      FT_LAUNCH_CHECK();
+      hipLaunchKernelGGL((decode_attn_merge_rows_kernel<E, D>), dim3((unsigned)hq, B), dim3(D), 0, ft_stream(),
+                         cptr<float>(part), mptr<T>(o), cptr<int>(pos0), t, max_keys, max_chunks, (int)hq);
+    }
+  }));
+  FT_LAUNCH_CHECK();
 }
 
 }  // namespace
 
-// decode_qkv_append_rows_ with t read from ctl[CTL_T] on the device: row b goes to position
-// pos0[b] + t. The host does not know t, so the only bound here is the capacity: a position outside
-// the cache or the RoPE tables writes nothing (the caller checks its own count of steps).
-void decode_qkv_append_rows_dev_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
-                                 const at::Tensor& pos0, const at::Tensor& ctl, const at::Tensor& k_cache,
-                                 const at::Tensor& v_cache) {
-  const char* op = "decode_qkv_append_rows_dev_";
-  check_rows(op, qkv, k_cache, v_cache, pos0);
-  check_ctl(op, ctl, qkv);
-  TORCH_CHECK(qkv.is_contiguous(), op, ": qkv must be contiguous");
-  const int64_t B = qkv.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
-  TORCH_CHECK(d > 0 && d % 8 == 0, op, ": head_dim must be a multiple of 8");
-  TORCH_CHECK(qkv.size(1) % d == 0 && qkv.size(1) / d > 2 * hkv, op, ": qkv width");
-  const int64_t hq = qkv.size(1) / d - 2 * hkv;
-  for (const at::Tensor* c : {&cos_t, &sin_t}) {
-    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() && c->scalar_type() == at::kFloat && c->is_contiguous() &&
-                    c->dim() == 2 && c->size(1) == d / 2 && c->size(0) == cos_t.size(0),
-                op, ": cos / sin must be fp32 [S, D / 2] on qkv's device");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": cos / sin alignment");
-  }
+// y[N] = w[N, K] x[K] (+ residual[N]), fp32 accumulation, one rounding per output.
+at::Tensor gemv(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
+  return gemv_impl<false>("gemv", false, x, w, residual);
+}
+
+// a[H] = silu(w1 x) * (w3 x) from the fused [w1; w3] view [2H, K].
+at::Tensor gemv_swiglu(const at::Tensor& x, const at::Tensor& w13) {
+  return gemv_impl<true>("gemv_swiglu", false, x, w13, c10::nullopt);
+}
+
+// y[R, N] = x[R, K] w[N, K]^T (+ residual[R, N]); row r has the bits of gemv(x[r], w, residual[r]).
+at::Tensor gemv_rows(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
+  return gemv_impl<false>("gemv_rows", true, x, w, residual);
+}
+
+// a[R, H]: row r has the bits of gemv_swiglu(x[r], w13).
+at::Tensor gemv_swiglu_rows(const at::Tensor& x, const at::Tensor& w13) {
+  return gemv_impl<true>("gemv_swiglu_rows", true, x, w13, c10::nullopt);
+}
+
+// qkv [(hq + 2 hkv) d] of the token at `pos`: Q rotated in place, K rotated into k_cache[:, pos],
+// V copied into v_cache[:, pos]. Caches: [hkv, Smax, d].
+void decode_qkv_append_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t, int64_t pos,
+                        const at::Tensor& k_cache, const at::Tensor& v_cache) {
+  const char* op = "decode_qkv_append_";
+  const KvShape s = check_kvm(op, qkv, k_cache, v_cache, false, false);
+  const int64_t hq = qkv_heads(op, qkv.numel(), s);
+  TORCH_CHECK(pos >= 0 && pos < s.smax, op, ": pos ", pos, " outside the cache [0, ", s.smax, ")");
+  check_rope(op, cos_t, sin_t, qkv, s.d, pos + 1);
   const at::DeviceGuard guard(qkv.device());
-  const int nvec = (int)(qkv.size(1) / 8);
+  const int nvec = (int)(qkv.numel() / 8);
   FT_DISPATCH_E(qkv.scalar_type(),
-                hipLaunchKernelGGL(qkv_append_rows_dev_kernel<E>, dim3((nvec + 255) / 256, (unsigned)B), dim3(256), 0,
-                                   ft_stream(), mptr<typename E::T>(qkv), cptr<float>(cos_t), cptr<float>(sin_t),
-                                   cptr<int>(pos0), cptr<int>(ctl), mptr<typename E::T>(k_cache),
-                                   mptr<typename E::T>(v_cache), (int)hq, (int)hkv, (int)d, (long)smax,
-                                   (long)std::min<int64_t>(smax, cos_t.size(0))));
+                hipLaunchKernelGGL(qkv_append_kernel<E>, dim3((nvec + 255) / 256), dim3(256), 0, ft_stream(),
+                                   mptr<typename E::T>(qkv), cptr<float>(cos_t) + pos * (s.d / 2),
+                                   cptr<float>(sin_t) + pos * (s.d / 2), mptr<typename E::T>(k_cache),
+                                   mptr<typename E::T>(v_cache), (int)hq, (int)s.hkv, (int)s.d, (long)s.smax,
+                                   (long)pos));
   FT_LAUNCH_CHECK();
 }
 
+// decode_qkv_append_ on row b of qkv [B, (hq + 2 hkv) d] at position pos0[b] + t of caches
+// [B, hkv, Smax, d]. max_pos is the caller's largest pos0[b] + t: the op checks it against Smax and
+// the RoPE tables and does not read pos0 back (a row beyond max_pos is left unwritten).
+void decode_qkv_append_rows_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
+                             const at::Tensor& pos0, int64_t t, int64_t max_pos, const at::Tensor& k_cache,
+                             const at::Tensor& v_cache) {
+  append_rows("decode_qkv_append_rows_", qkv, cos_t, sin_t, pos0, nullptr, t, max_pos, k_cache, v_cache);
+}
+
+// decode_qkv_append_rows_ with t read from ctl[CTL_T] on the device: row b goes to position
+// pos0[b] + t; a position outside the cache or the RoPE tables writes nothing.
+void decode_qkv_append_rows_dev_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
+                                 const at::Tensor& pos0, const at::Tensor& ctl, const at::Tensor& k_cache,
+                                 const at::Tensor& v_cache) {
+  append_rows("decode_qkv_append_rows_dev_", qkv, cos_t, sin_t, pos0, &ctl, 0, 0, k_cache, v_cache);
+}
+
+// o[hq d] = softmax(q K^T / sqrt(d)) V over keys 0 .. n_keys-1 of the caches [hkv, Smax, d].
+at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t n_keys) {
+  const char* op = "decode_attn";
+  const KvShape s = check_kvm(op, q, k_cache, v_cache, false, true);
+  const int64_t hq = q_heads(op, q.numel(), s);
+  TORCH_CHECK(n_keys >= 1 && n_keys <= s.smax, op, ": n_keys ", n_keys, " outside [1, Smax = ", s.smax, "]");
+  const at::DeviceGuard guard(q.device());
+  const int nchunks = (int)((n_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
+  TORCH_CHECK(nchunks <= 65535, op, ": too many key chunks");
+  auto part = at::empty({nchunks, hq, s.d + 2}, q.options().dtype(at::kFloat));
+  auto o = at::empty({hq * s.d}, q.options());
+  const int G = (int)(hq / s.hkv);
+  FT_DISPATCH_E(q.scalar_type(), FT_DECODE_D(s.d, {
+    typedef typename E::T T;
+    const float scale = 1.f / sqrtf((float)D);
+    FT_DECODE_GT(G, hipLaunchKernelGGL((decode_attn_kernel<E, D, GT>), dim3((unsigned)s.hkv, nchunks), dim3(256), 0,
+                                       ft_stream(), cptr<T>(q), cptr<T>(k_cache), cptr<T>(v_cache), mptr<float>(part),
+                                       (int)hq, (int)s.hkv, (long)s.smax, (int)n_keys, scale));
+    FT_LAUNCH_CHECK();
+    hipLaunchKernelGGL((decode_attn_merge_kernel<E, D>), dim3((unsigned)hq), dim3(D), 0, ft_stream(),
+                       cptr<float>(part), mptr<T>(o), (int)hq, nchunks);
+  }));
+  FT_LAUNCH_CHECK();
+  return o;
+}
+
+// o[B, hq d]: q [B, hq d] may be a column slice of a wider buffer (rows stride(0) apart); row b is
+// decode_attn of q[b] over keys 0 .. pos0[b] + t of its caches [B, hkv, Smax, d],
+// bit for bit. max_keys is the caller's largest key count (pos0 is not read back).
+at::Tensor decode_attn_rows(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                            const at::Tensor& pos0, int64_t t, int64_t max_keys) {
+  const char* op = "decode_attn_rows";
+  const KvShape s = check_kvm(op, q, k_cache, v_cache, true, true);
+  check_pos0(op, pos0, q);
+  const int64_t hq = q_heads(op, q.size(1), s);
+  TORCH_CHECK(t >= 0 && t <= INT_MAX && max_keys > t && max_keys <= s.smax, op, ": max_keys ", max_keys, " (t = ", t,
+              ") outside [t + 1, Smax = ", s.smax, "]");
+  const at::DeviceGuard guard(q.device());
+  const int max_chunks = (int)((max_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
+  TORCH_CHECK(max_chunks <= 65535, op, ": too many key chunks");
+  auto part = at::empty({q.size(0), max_chunks, hq, s.d + 2}, q.options().dtype(at::kFloat));
+  auto o = at::empty({q.size(0), hq * s.d}, q.options());
+  attn_rows_into(q, k_cache, v_cache, pos0, nullptr, (int)t, (int)max_keys, max_chunks, s, hq, part, o);
+  return o;
+}
+
 // decode_attn_rows with t read from ctl[CTL_T] on the device, into the caller's buffers: part fp32
-// [B, ceil(Smax / DECODE_CHUNK), hq, d + 2] and o [B, hq d]. The grid covers the capacity, a row's
-// merge folds the chunks its key count min(pos0[b] + t + 1, Smax) needs: the bits of decode_attn_rows.
+// [B, ceil(Smax / DECODE_CHUNK), hq, d + 2] and o [B, hq d].
 void decode_attn_rows_dev(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                           const at::Tensor& pos0, const at::Tensor& ctl, const at::Tensor& part, const at::Tensor& o) {
   const char* op = "decode_attn_rows_dev";
-  check_rows(op, q, k_cache, v_cache, pos0);
+  const KvShape s = check_kvm(op, q, k_cache, v_cache, true, true);
+  check_pos0(op, pos0, q);
   check_ctl(op, ctl, q);
-  const int64_t B = q.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
-  TORCH_CHECK(d == 64 || d == 128, op, ": head_dim must be 64 or 128");
-  TORCH_CHECK(q.size(1) % d == 0, op, ": q width");
-  const int64_t hq = q.size(1) / d;
-  TORCH_CHECK(hq > 0 && hq % hkv == 0, op, ": Hq must be a multiple of Hkv");
-  TORCH_CHECK(smax >= 1, op, ": empty cache");
-  const int64_t max_chunks = (smax + DECODE_CHUNK - 1) / DECODE_CHUNK;
+  const int64_t hq = q_heads(op, q.size(1), s);
+  const int64_t max_chunks = (s.smax + DECODE_CHUNK - 1) / DECODE_CHUNK;
   TORCH_CHECK(max_chunks <= 65535, op, ": too many key chunks");
-  TORCH_CHECK(part.is_cuda() && part.device() == q.device() && part.scalar_type() == at::kFloat &&
-                  part.is_contiguous() && part.numel() == B * max_chunks * hq * (d + 2),
-              op, ": part must be a contiguous fp32 [B, ceil(Smax / ", DECODE_CHUNK, "), Hq, D + 2] tensor");
-  TORCH_CHECK(o.is_cuda() && o.device() == q.device() && o.scalar_type() == q.scalar_type() && o.is_contiguous() &&
-                  o.dim() == 2 && o.size(0) == B && o.size(1) == hq * d,
-              op, ": o must be a contiguous [B, Hq D] tensor of q's dtype");
+  check_attn_out(op, q, part, o, max_chunks, hq, s.d);
   const at::DeviceGuard guard(q.device());
-  FT_DISPATCH_E(q.scalar_type(), {
-    if (d == 64)
-      launch_attn_rows_dev<E, 64>(q, k_cache, v_cache, part, o, pos0, ctl, (int)max_chunks, (int)B, (int)hq, (int)hkv);
-    else
-      launch_attn_rows_dev<E, 128>(q, k_cache, v_cache, part, o, pos0, ctl, (int)max_chunks, (int)B, (int)hq,
-                                   (int)hkv);
-  });
+  attn_rows_into(q, k_cache, v_cache, pos0, &ctl, 0, (int)s.smax, (int)max_chunks, s, hq, part, o);
+}
+
+// Keys per workgroup of decode_attn (the tests place n_keys around its multiples).
+int64_t decode_attn_chunk() { return DECODE_CHUNK; }
+
+// out[r] = one token drawn from row r of logits [R, V]; a pure function of
+// (logits, temperature, top_k, top_p, key, step, r). temperature 0: the lowest column of the row maximum.
+// top_p in (0, 1]; 1 (the default) runs no nucleus pass.
+void sample_(const at::Tensor& logits, const at::Tensor& out, double temperature, int64_t top_k, int64_t key,
+             int64_t step, double top_p) {
+  FT_CHECK_CUDA(logits);
+  FT_CHECK_MODEL_DTYPE(logits);
+  FT_CHECK_CONTIG(logits);
+  FT_CHECK_CUDA(out);
+  FT_CHECK_CONTIG(out);
+  TORCH_CHECK(out.scalar_type() == at::kLong && out.device() == logits.device(), "sample_: out must be int64 on logits' device");
+  TORCH_CHECK(logits.dim() >= 1 && logits.size(-1) > 0, "sample_: logits must be [R, V]");
+  const int64_t V = logits.size(-1);
+  TORCH_CHECK(V % 8 == 0, "sample_: vocab must be a multiple of 8");
+  const int64_t R = logits.numel() / V;
+  TORCH_CHECK(V <= INT_MAX && R <= INT_MAX, "sample_: R and V must fit 32 bits");
+  TORCH_CHECK(out.numel() == R, "sample_: out shape mismatch");
+  TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY, "sample_: temperature must be finite and >= 0");
+  TORCH_CHECK(top_k >= 0, "sample_: top_k must be >= 0 (0: all columns)");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0 && (float)top_p > 0.f, "sample_: top_p must be in (0, 1]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "sample_: logits must be 16-byte aligned");
+  const at::DeviceGuard guard(logits.device());
+  const uint64_t k64 = (uint64_t)key;
+  if (R > 0)
+    FT_DISPATCH_E(logits.scalar_type(),
+                  hipLaunchKernelGGL(sample_kernel<E>, dim3((unsigned)std::min<int64_t>(R, SAMPLE_MAX_BLOCKS)), dim3(256),
+                                     0, ft_stream(), cptr<typename E::T>(logits), mptr<int64_t>(out), (int)V, (int)R,
+                                     (float)temperature, (int)std::min<int64_t>(top_k, V), (float)top_p,
+                                     (uint32_t)k64, (uint32_t)(k64 >> 32), (uint32_t)(uint64_t)step));
   FT_LAUNCH_CHECK();
 }
 
@@ -1148,183 +1164,6 @@ void decode_ctl_advance_(const at::Tensor& ctl) {
   check_ctl("decode_ctl_advance_", ctl, ctl);
   const at::DeviceGuard guard(ctl.device());
   hipLaunchKernelGGL(ctl_advance_kernel, dim3(1), dim3(64), 0, ft_stream(), mptr<int>(ctl));
-  FT_LAUNCH_CHECK();
-}
-
-// y[R, N] = x[R, K] w[N, K]^T (+ residual[R, N]); row r has the bits of gemv(x[r], w, residual[r]).
-at::Tensor gemv_rows(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
-  return gemv_rows_impl<false>("gemv_rows", x, w, residual);
-}
-
-// a[R, H]: row r has the bits of gemv_swiglu(x[r], w13).
-at::Tensor gemv_swiglu_rows(const at::Tensor& x, const at::Tensor& w13) {
-  return gemv_rows_impl<true>("gemv_swiglu_rows", x, w13, c10::nullopt);
-}
-
-// decode_qkv_append_ on row b of qkv [B, (hq + 2 hkv) d] at position pos0[b] + t of caches
-// [B, hkv, Smax, d]. max_pos is the caller's largest pos0[b] + t: the op checks it against Smax and
-// the RoPE tables and does not read pos0 back (a row beyond max_pos is left unwritten).
-void decode_qkv_append_rows_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t,
-                             const at::Tensor& pos0, int64_t t, int64_t max_pos, const at::Tensor& k_cache,
-                             const at::Tensor& v_cache) {
-  const char* op = "decode_qkv_append_rows_";
-  check_rows(op, qkv, k_cache, v_cache, pos0);
-  TORCH_CHECK(qkv.is_contiguous(), op, ": qkv must be contiguous");
-  const int64_t B = qkv.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
-  TORCH_CHECK(d > 0 && d % 8 == 0, op, ": head_dim must be a multiple of 8");
-  TORCH_CHECK(qkv.size(1) % d == 0 && qkv.size(1) / d > 2 * hkv, op, ": qkv width");
-  const int64_t hq = qkv.size(1) / d - 2 * hkv;
-  TORCH_CHECK(t >= 0 && t <= INT_MAX && max_pos >= t && max_pos < smax, op, ": largest position ", max_pos,
-              " (t = ", t, ") outside the cache [0, ", smax, ")");
-  for (const at::Tensor* c : {&cos_t, &sin_t}) {
-    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() && c->scalar_type() == at::kFloat && c->is_contiguous() &&
-                    c->dim() == 2 && c->size(1) == d / 2 && c->size(0) > max_pos,
-                op, ": cos / sin must be fp32 [S > largest position, D / 2] on qkv's device");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": cos / sin alignment");
-  }
-  const at::DeviceGuard guard(qkv.device());
-  const int nvec = (int)(qkv.size(1) / 8);
-  FT_DISPATCH_E(qkv.scalar_type(),
-                hipLaunchKernelGGL(qkv_append_rows_kernel<E>, dim3((nvec + 255) / 256, (unsigned)B), dim3(256), 0,
-                                   ft_stream(), mptr<typename E::T>(qkv), cptr<float>(cos_t), cptr<float>(sin_t),
-                                   cptr<int>(pos0), (int)t, mptr<typename E::T>(k_cache),
-                                   mptr<typename E::T>(v_cache), (int)hq, (int)hkv, (int)d, (long)smax,
-                                   (long)(max_pos + 1)));
-  FT_LAUNCH_CHECK();
-}
-
-// o[B, hq d]: q [B, hq d] may be a column slice of a wider buffer (rows stride(0) apart); row b is
-// decode_attn of q[b] over keys 0 .. pos0[b] + t of its caches [B, hkv, Smax, d],
-// bit for bit. max_keys is the caller's largest key count (pos0 is not read back).
-at::Tensor decode_attn_rows(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                            const at::Tensor& pos0, int64_t t, int64_t max_keys) {
-  const char* op = "decode_attn_rows";
-  check_rows(op, q, k_cache, v_cache, pos0);
-  const int64_t B = q.size(0), hkv = k_cache.size(1), smax = k_cache.size(2), d = k_cache.size(3);
-  TORCH_CHECK(d == 64 || d == 128, op, ": head_dim must be 64 or 128");
-  TORCH_CHECK(q.size(1) % d == 0, op, ": q width");
-  const int64_t hq = q.size(1) / d;
-  TORCH_CHECK(hq > 0 && hq % hkv == 0, op, ": Hq must be a multiple of Hkv");
-  TORCH_CHECK(t >= 0 && t <= INT_MAX && max_keys > t && max_keys <= smax, op, ": max_keys ", max_keys, " (t = ", t,
-              ") outside [t + 1, Smax = ", smax, "]");
-  const at::DeviceGuard guard(q.device());
-  const int max_chunks = (int)((max_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
-  TORCH_CHECK(max_chunks <= 65535, op, ": too many key chunks");
-  auto part = at::empty({B, max_chunks, hq, d + 2}, q.options().dtype(at::kFloat));
-  auto o = at::empty({B, hq * d}, q.options());
-  FT_DISPATCH_E(q.scalar_type(), {
-    if (d == 64)
-      launch_attn_rows<E, 64>(q, k_cache, v_cache, part, o, pos0, (int)t, (int)max_keys, max_chunks, (int)B, (int)hq,
-                              (int)hkv);
-    else
-      launch_attn_rows<E, 128>(q, k_cache, v_cache, part, o, pos0, (int)t, (int)max_keys, max_chunks, (int)B, (int)hq,
-                               (int)hkv);
-  });
-  FT_LAUNCH_CHECK();
-  return o;
-}
-
-// y[N] = w[N, K] x[K] (+ residual[N]), fp32 accumulation, one rounding per output.
-at::Tensor gemv(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& residual) {
-  return gemv_impl<false>("gemv", x, w, residual);
-}
-
-// a[H] = silu(w1 x) * (w3 x) from the fused [w1; w3] view [2H, K].
-at::Tensor gemv_swiglu(const at::Tensor& x, const at::Tensor& w13) {
-  return gemv_impl<true>("gemv_swiglu", x, w13, c10::nullopt);
-}
-
-// qkv [(hq + 2 hkv) d] of the token at `pos`: Q rotated in place, K rotated into k_cache[:, pos],
-// V copied into v_cache[:, pos]. Caches: [hkv, Smax, d].
-void decode_qkv_append_(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t, int64_t pos,
-                        const at::Tensor& k_cache, const at::Tensor& v_cache) {
-  FT_CHECK_MODEL_DTYPE(qkv);
-  check_vec("decode_qkv_append_", qkv, "qkv");
-  TORCH_CHECK(k_cache.dim() == 3, "decode_qkv_append_: a cache is [Hkv, Smax, D]");
-  const int64_t hkv = k_cache.size(0), smax = k_cache.size(1), d = k_cache.size(2);
-  check_cache("decode_qkv_append_", k_cache, qkv, hkv, d);
-  check_cache("decode_qkv_append_", v_cache, qkv, hkv, d);
-  TORCH_CHECK(v_cache.size(1) == smax, "decode_qkv_append_: k_cache / v_cache length mismatch");
-  TORCH_CHECK(d > 0 && d % 8 == 0, "decode_qkv_append_: head_dim must be a multiple of 8");
-  TORCH_CHECK(qkv.numel() % d == 0 && qkv.numel() / d > 2 * hkv, "decode_qkv_append_: qkv width");
-  const int64_t hq = qkv.numel() / d - 2 * hkv;
-  TORCH_CHECK(pos >= 0 && pos < smax, "decode_qkv_append_: pos ", pos, " outside the cache [0, ", smax, ")");
-  for (const at::Tensor* t : {&cos_t, &sin_t}) {
-    TORCH_CHECK(t->is_cuda() && t->device() == qkv.device() && t->scalar_type() == at::kFloat && t->is_contiguous() &&
-                    t->dim() == 2 && t->size(1) == d / 2 && t->size(0) > pos,
-                "decode_qkv_append_: cos / sin must be fp32 [S > pos, D / 2] on qkv's device");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "decode_qkv_append_: cos / sin alignment");
-  }
-  const at::DeviceGuard guard(qkv.device());
-  const int nvec = (int)(qkv.numel() / 8);
-  FT_DISPATCH_E(qkv.scalar_type(),
-                hipLaunchKernelGGL(qkv_append_kernel<E>, dim3((nvec + 255) / 256), dim3(256), 0, ft_stream(),
-                                   mptr<typename E::T>(qkv), cptr<float>(cos_t) + pos * (d / 2),
-                                   cptr<float>(sin_t) + pos * (d / 2), mptr<typename E::T>(k_cache),
-                                   mptr<typename E::T>(v_cache), (int)hq, (int)hkv, (int)d, (long)smax, (long)pos));
-  FT_LAUNCH_CHECK();
-}
-
-// o[hq d] = softmax(q K^T / sqrt(d)) V over keys 0 .. n_keys-1 of the caches [hkv, Smax, d].
-at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache, int64_t n_keys) {
-  FT_CHECK_MODEL_DTYPE(q);
-  check_vec("decode_attn", q, "q");
-  TORCH_CHECK(k_cache.dim() == 3, "decode_attn: a cache is [Hkv, Smax, D]");
-  const int64_t hkv = k_cache.size(0), smax = k_cache.size(1), d = k_cache.size(2);
-  check_cache("decode_attn", k_cache, q, hkv, d);
-  check_cache("decode_attn", v_cache, q, hkv, d);
-  TORCH_CHECK(v_cache.size(1) == smax, "decode_attn: k_cache / v_cache length mismatch");
-  TORCH_CHECK(d == 64 || d == 128, "decode_attn: head_dim must be 64 or 128");
-  TORCH_CHECK(q.numel() % d == 0, "decode_attn: q width");
-  const int64_t hq = q.numel() / d;
-  TORCH_CHECK(hq > 0 && hq % hkv == 0, "decode_attn: Hq must be a multiple of Hkv");
-  TORCH_CHECK(n_keys >= 1 && n_keys <= smax && smax <= INT_MAX, "decode_attn: n_keys ", n_keys,
-              " outside [1, Smax = ", smax, "]");
-  const at::DeviceGuard guard(q.device());
-  const int nchunks = (int)((n_keys + DECODE_CHUNK - 1) / DECODE_CHUNK);
-  TORCH_CHECK(nchunks <= 65535, "decode_attn: too many key chunks");
-  auto part = at::empty({nchunks, hq, d + 2}, q.options().dtype(at::kFloat));
-  auto o = at::empty({hq * d}, q.options());
-  FT_DISPATCH_E(q.scalar_type(), {
-    if (d == 64) launch_attn<E, 64>(q, k_cache, v_cache, part, o, (int)hq, (int)hkv, (int)n_keys, nchunks);
-    else launch_attn<E, 128>(q, k_cache, v_cache, part, o, (int)hq, (int)hkv, (int)n_keys, nchunks);
-  });
-  FT_LAUNCH_CHECK();
-  return o;
-}
-
-// Keys per workgroup of decode_attn (the tests place n_keys around its multiples).
-int64_t decode_attn_chunk() { return DECODE_CHUNK; }
-
-// out[r] = one token drawn from row r of logits [R, V]; a pure function of
-// (logits, temperature, top_k, top_p, key, step, r). temperature 0: the lowest column of the row maximum.
-// top_p in (0, 1]; 1 (the default) runs no nucleus pass.
-void sample_(const at::Tensor& logits, const at::Tensor& out, double temperature, int64_t top_k, int64_t key,
-             int64_t step, double top_p) {
-  FT_CHECK_CUDA(logits);
-  FT_CHECK_MODEL_DTYPE(logits);
-  FT_CHECK_CONTIG(logits);
-  FT_CHECK_CUDA(out);
-  FT_CHECK_CONTIG(out);
-  TORCH_CHECK(out.scalar_type() == at::kLong && out.device() == logits.device(), "sample_: out must be int64 on logits' device");
-  TORCH_CHECK(logits.dim() >= 1 && logits.size(-1) > 0, "sample_: logits must be [R, V]");
-  const int64_t V = logits.size(-1);
-  TORCH_CHECK(V % 8 == 0, "sample_: vocab must be a multiple of 8");
-  const int64_t R = logits.numel() / V;
-  TORCH_CHECK(V <= INT_MAX && R <= INT_MAX, "sample_: R and V must fit 32 bits");
-  TORCH_CHECK(out.numel() == R, "sample_: out shape mismatch");
-  TORCH_CHECK(temperature >= 0.0 && temperature < INFINITY, "sample_: temperature must be finite and >= 0");
-  TORCH_CHECK(top_k >= 0, "sample_: top_k must be >= 0 (0: all columns)");
-  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0 && (float)top_p > 0.f, "sample_: top_p must be in (0, 1]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "sample_: logits must be 16-byte aligned");
-  const at::DeviceGuard guard(logits.device());
-  const uint64_t k64 = (uint64_t)key;
-  if (R > 0)
-    FT_DISPATCH_E(logits.scalar_type(),
-                  hipLaunchKernelGGL(sample_kernel<E>, dim3((unsigned)std::min<int64_t>(R, SAMPLE_MAX_BLOCKS)), dim3(256),
-                                     0, ft_stream(), cptr<typename E::T>(logits), mptr<int64_t>(out), (int)V, (int)R,
-                                     (float)temperature, (int)std::min<int64_t>(top_k, V), (float)top_p,
-                                     (uint32_t)k64, (uint32_t)(k64 >> 32), (uint32_t)(uint64_t)step));
   FT_LAUNCH_CHECK();
 }
 

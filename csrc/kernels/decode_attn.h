@@ -1,7 +1,7 @@
-// What the decode attention kernels of decode.hip (model-dtype cache) and decode_kv8.hip (FP8 cache)
-// share: the chunk size, the control block of the device-step ops, a row's key count, and the merge
-// of the per-chunk partials (acc[D] unnormalised, m, l) in chunk order. Both files leave their
-// partials in the same `part` layout, [chunks, Hq, D + 2], so one merge serves both.
+// What the cache kernels of decode.hip (model-dtype cache) and decode_kv8.hip (FP8 cache) share: the
+// chunk size, the control block of the device-step ops, a row's key count, the RoPE rotation of the
+// appends, and the merge of the per-chunk partials (acc[D] unnormalised, m, l) in chunk order. Both
+// files leave their partials in the same `part` layout, [chunks, Hq, D + 2], so one merge serves both.
 #pragma once
 
 #include "common.h"
@@ -29,6 +29,19 @@ enum : int {
 // against Smax; pos0 itself is never read back). Below 1 no workgroup of the row does anything.
 __device__ __forceinline__ int row_keys(const int* __restrict__ pos0, int b, int t, int max_keys) {
   return (int)min((long)pos0[b] + t + 1, (long)max_keys);
+}
+
+// RoPE on 8 columns of a head, four (even, odd) pairs: c and s are the cos and sin of the four pairs'
+// angles. The appends of both cache formats rotate with this, so a K row has the same bits before
+// either of them stores it.
+__device__ __forceinline__ void rope8(const float* x, const float4& c, const float4& s, float* r) {
+  const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const float a = x[2 * p], b = x[2 * p + 1];
+    r[2 * p] = a * cc[p] - b * ss[p];
+    r[2 * p + 1] = a * ss[p] + b * cc[p];
+  }
 }
 
 // One workgroup per query head, one thread per dim: the chunk partials in chunk order.

@@ -11,9 +11,9 @@
 //
 // Quantizing: a thread owns 8 columns, so a head row is D / 8 adjacent lanes of one wave. The row's
 // amax is an xor butterfly over those lanes on the bit patterns of |x| (integer order = float order
-// for non-negative floats, NaN and infinity on top), the two IEEE divisions and the packed encode are
-// decode_w8.hip's quantize_rows_kernel's, each lane stores its 8 codes as one 8-byte store and the
-// row's first lane the scale. No LDS, no barrier.
+// for non-negative floats, NaN and infinity on top), inv and the scale come from it by fp8.h's e4m3_row
+// (the rule of decode_w8.hip's weight quantizer), each lane stores its 8 codes as one 8-byte store and
+// the row's first lane the scale. No LDS, no barrier.
 //
 // Attention: the grid, the chunks of DECODE_CHUNK keys, the (acc, m, l) partials and the `part` layout
 // are decode.hip's, so its merge kernels (decode_attn.h) fold the chunks. The chunk kernel is written
@@ -33,11 +33,8 @@
 //
 // The q K and P V products stay on the vector ALU in fp32: an FP8 MFMA would need the query (and the
 // probabilities) quantized as well, which is another numerics contract.
-#include <climits>
-
-#include "decode_attn.h"
+#include "decode_host.h"  // the operand checks and dispatch macros; decode_attn.h
 #include "fp8.h"
-#include "torch_utils.h"
 
 namespace {
 
@@ -54,28 +51,21 @@ __device__ __forceinline__ void quantize_head_row(const float* x, uint8_t* __res
   for (int j = 0; j < 8; ++j) m = max(m, __float_as_uint(x[j]) & 0x7fffffffu);
 #pragma unroll
   for (int o = LPR / 2; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-  const bool finite = m < 0x7f800000u;
-  const float amax = __uint_as_float(m);
-  // amax == 0: scale 1, the codes are the signed zeros. A non-finite row: NaN scale, zero codes.
-  float inv = 0.f, sc = __uint_as_float(0x7fc00000u);
-  if (finite) {
-    inv = m == 0u ? 1.f : fminf(__fdiv_rn(448.f, amax), 3.402823466e+38f);
-    sc = m == 0u ? 1.f : __fdiv_rn(amax, 448.f);
-  }
+  const E4m3Row q = e4m3_row(m);
   uint2 c = make_uint2(0u, 0u);
-  if (finite) {
+  if (q.finite) {
     float f[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = __fmul_rn(x[j], inv);
+    for (int j = 0; j < 8; ++j) f[j] = __fmul_rn(x[j], q.inv);
     c = make_uint2(f32x4_to_fp8(f), f32x4_to_fp8(f + 4));
   }
   *reinterpret_cast<uint2*>(codes8) = c;
-  if (first) *scale = sc;
+  if (first) *scale = q.scale;
 }
 
 // decode_qkv_append_kv8_: vector i (8 columns) of qkv [(Hq + 2 Hkv) D] of the token at `pos`. The
-// rotation is decode.hip's qkv_append_vec's, expression for expression; K is then rounded to the model
-// dtype, as the model-dtype cache stores it, before it is quantized.
+// rotation is decode.hip's qkv_append_vec's (rope8); K is then rounded to the model dtype, as the
+// model-dtype cache stores it, before it is quantized.
 template <class E, int D>
 __device__ __forceinline__ void qkv_append_kv8_vec(int i, typename E::T* __restrict__ qkv,
                                                    const float* __restrict__ cos_row,
@@ -86,16 +76,9 @@ __device__ __forceinline__ void qkv_append_kv8_vec(int i, typename E::T* __restr
   float x[8];
   ld8<E>(qkv + col, x);
   if (head < hq + hkv) {
-    const float4 c = *reinterpret_cast<const float4*>(cos_row + (within >> 1));
-    const float4 s = *reinterpret_cast<const float4*>(sin_row + (within >> 1));
-    const float cc[4] = {c.x, c.y, c.z, c.w}, ss[4] = {s.x, s.y, s.z, s.w};
     float r[8];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const float a = x[2 * p], b = x[2 * p + 1];
-      r[2 * p] = a * cc[p] - b * ss[p];
-      r[2 * p + 1] = a * ss[p] + b * cc[p];
-    }
+    rope8(x, *reinterpret_cast<const float4*>(cos_row + (within >> 1)),
+          *reinterpret_cast<const float4*>(sin_row + (within >> 1)), r);
     if (head < hq) {
       st8<E>(qkv + col, r);
     } else {
@@ -376,107 +359,21 @@ __global__ __launch_bounds__(256) void decode_attn_rows_dev_kv8_kernel(
 // --------------------------------------------------------------------------------------------
 // Host side
 // --------------------------------------------------------------------------------------------
-// The activation x ([width] for lead == 0, else [B, width]) and the four cache tensors: codes uint8
-// [lead.., Hkv, Smax, D], scales fp32 [lead.., Hkv, Smax], all on x's device. Returns (Hkv, Smax, D).
-struct KvShape {
-  int64_t hkv, smax, d;
-};
-
+// check_kv of decode_host.h for a cache of codes uint8 [lead.., Hkv, Smax, D], with what the FP8 cache
+// adds: a 16-bit activation, the scales fp32 [lead.., Hkv, Smax], and head_dim 64 or 128 for every op.
 KvShape check_kv8(const char* op, const at::Tensor& x, const at::Tensor& kc, const at::Tensor& vc,
                   const at::Tensor& ks, const at::Tensor& vs, bool rows) {
-  TORCH_CHECK(x.is_cuda() && (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf), op,
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, op,
               ": the activation must be a bf16 or fp16 GPU tensor");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, op, ": the activation must be 16-byte aligned");
-  const int lead = rows ? 1 : 0;
-  if (rows) {
-    TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(0) <= 65535 && x.stride(1) == 1 &&
-                    x.stride(0) >= x.size(1) && x.stride(0) % 8 == 0,
-                op, ": the activation is [B, width], 1 <= B <= 65535, rows dense and a multiple of 8 elements apart");
-  } else {
-    TORCH_CHECK(x.dim() == 1 && x.is_contiguous(), op, ": the activation is a contiguous [width] tensor");
-  }
-  TORCH_CHECK(kc.dim() == 3 + lead, op, rows ? ": a cache is [B, Hkv, Smax, D]" : ": a cache is [Hkv, Smax, D]");
-  for (const at::Tensor* c : {&kc, &vc}) {
-    TORCH_CHECK(c->is_cuda() && c->device() == x.device() && c->scalar_type() == at::kByte && c->is_contiguous() &&
-                    c->sizes() == kc.sizes(),
-                op, ": the caches are contiguous uint8 (e4m3 codes) tensors of one shape on the activation's device");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": a cache must be 16-byte aligned");
-  }
+  const KvShape r = check_kv(op, x, kc, vc, at::kByte, rows);
   for (const at::Tensor* s : {&ks, &vs}) {
     TORCH_CHECK(s->is_cuda() && s->device() == x.device() && s->scalar_type() == at::kFloat && s->is_contiguous() &&
-                    s->dim() == 2 + lead && s->sizes() == kc.sizes().slice(0, 2 + lead),
+                    s->sizes() == kc.sizes().slice(0, kc.dim() - 1),
                 op, ": the scales are contiguous fp32 tensors of the caches' shape without D, on their device");
   }
-  TORCH_CHECK(!rows || kc.size(0) == x.size(0), op, ": the caches hold one sequence per activation row");
-  const KvShape r{kc.size(lead), kc.size(lead + 1), kc.size(lead + 2)};
   TORCH_CHECK(r.d == 64 || r.d == 128, op, ": head_dim must be 64 or 128");
-  TORCH_CHECK(r.hkv >= 1 && r.smax >= 1 && r.smax <= INT_MAX, op, ": empty cache, or Smax beyond 32 bits");
   return r;
 }
-
-void check_pos0(const char* op, const at::Tensor& pos0, const at::Tensor& x) {
-  TORCH_CHECK(pos0.is_cuda() && pos0.device() == x.device() && pos0.scalar_type() == at::kInt &&
-                  pos0.is_contiguous() && pos0.dim() == 1 && pos0.size(0) == x.size(0),
-              op, ": pos0 must be a contiguous int32 [B] tensor on the activation's device");
-}
-
-void check_ctl(const char* op, const at::Tensor& ctl, const at::Tensor& like) {
-  TORCH_CHECK(ctl.is_cuda() && ctl.device() == like.device() && ctl.scalar_type() == at::kInt && ctl.is_contiguous() &&
-                  ctl.dim() == 1 && ctl.size(0) >= CTL_WORDS,
-              op, ": ctl must be a contiguous int32 tensor of at least ", (int)CTL_WORDS, " words on the operands' device");
-}
-
-// cos / sin: fp32 [S >= need, D / 2] on qkv's device
-void check_rope(const char* op, const at::Tensor& cos_t, const at::Tensor& sin_t, const at::Tensor& qkv, int64_t d,
-                int64_t need) {
-  for (const at::Tensor* c : {&cos_t, &sin_t}) {
-    TORCH_CHECK(c->is_cuda() && c->device() == qkv.device() && c->scalar_type() == at::kFloat && c->is_contiguous() &&
-                    c->dim() == 2 && c->size(1) == d / 2 && c->size(0) == cos_t.size(0) && c->size(0) >= need,
-                op, ": cos / sin must be fp32 [S, D / 2] on qkv's device, S beyond the largest position");
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0, op, ": cos / sin alignment");
-  }
-}
-
-// Hq of a qkv row of `width` elements
-int64_t qkv_heads(const char* op, int64_t width, const KvShape& s) {
-  TORCH_CHECK(width % s.d == 0 && width / s.d > 2 * s.hkv, op, ": qkv width");
-  return width / s.d - 2 * s.hkv;
-}
-
-int64_t q_heads(const char* op, int64_t width, const KvShape& s) {
-  TORCH_CHECK(width % s.d == 0 && width > 0 && (width / s.d) % s.hkv == 0, op,
-              ": q is [.., Hq D] with Hq a positive multiple of Hkv");
-  return width / s.d;
-}
-
-#define FT_KV8_D(d, ...)            \
-  do {                              \
-    if ((d) == 64) {                \
-      constexpr int D = 64;         \
-      __VA_ARGS__;                  \
-    } else {                        \
-      constexpr int D = 128;        \
-      __VA_ARGS__;                  \
-    }                               \
-  } while (0)
-
-// the GQA tile: the smallest of 1, 2, 4, 8 that holds the group, 8 beyond
-#define FT_KV8_GT(G, ...)           \
-  do {                              \
-    if ((G) == 1) {                 \
-      constexpr int GT = 1;         \
-      __VA_ARGS__;                  \
-    } else if ((G) == 2) {          \
-      constexpr int GT = 2;         \
-      __VA_ARGS__;                  \
-    } else if ((G) <= 4) {          \
-      constexpr int GT = 4;         \
-      __VA_ARGS__;                  \
-    } else {                        \
-      constexpr int GT = 8;         \
-      __VA_ARGS__;                  \
-    }                               \
-  } while (0)
 
 void append_kv8(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor& sin_t, int64_t pos,
                 const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& ks, const at::Tensor& vs) {
@@ -487,7 +384,7 @@ void append_kv8(const at::Tensor& qkv, const at::Tensor& cos_t, const at::Tensor
   check_rope(op, cos_t, sin_t, qkv, s.d, pos + 1);
   const at::DeviceGuard guard(qkv.device());
   const int nvec = (int)(qkv.numel() / 8);
-  FT_DISPATCH_E16(qkv.scalar_type(), FT_KV8_D(s.d, {
+  FT_DISPATCH_E16(qkv.scalar_type(), FT_DECODE_D(s.d, {
     hipLaunchKernelGGL((qkv_append_kv8_kernel<E, D>), dim3((nvec + 255) / 256), dim3(256), 0, ft_stream(),
                        mptr<typename E::T>(qkv), cptr<float>(cos_t) + pos * (D / 2),
                        cptr<float>(sin_t) + pos * (D / 2), mptr<uint8_t>(kc), mptr<uint8_t>(vc), mptr<float>(ks),
@@ -505,21 +402,11 @@ void append_rows_kv8(const char* op, const at::Tensor& qkv, const at::Tensor& co
   check_pos0(op, pos0, qkv);
   TORCH_CHECK(qkv.is_contiguous(), op, ": qkv must be contiguous");
   const int64_t B = qkv.size(0), hq = qkv_heads(op, qkv.size(1), s);
-  long limit;
-  if (ctl != nullptr) {
-    check_ctl(op, *ctl, qkv);
-    check_rope(op, cos_t, sin_t, qkv, s.d, 0);
-    limit = (long)std::min<int64_t>(s.smax, cos_t.size(0));
-  } else {
-    TORCH_CHECK(t >= 0 && t <= INT_MAX && max_pos >= t && max_pos < s.smax, op, ": largest position ", max_pos,
-                " (t = ", t, ") outside the cache [0, ", s.smax, ")");
-    check_rope(op, cos_t, sin_t, qkv, s.d, max_pos + 1);
-    limit = (long)(max_pos + 1);
-  }
+  const long limit = check_append_rows(op, qkv, cos_t, sin_t, ctl, t, max_pos, s);
   const at::DeviceGuard guard(qkv.device());
   const int nvec = (int)(qkv.size(1) / 8);
   const dim3 grid((nvec + 255) / 256, (unsigned)B);
-  FT_DISPATCH_E16(qkv.scalar_type(), FT_KV8_D(s.d, {
+  FT_DISPATCH_E16(qkv.scalar_type(), FT_DECODE_D(s.d, {
     if (ctl != nullptr)
       hipLaunchKernelGGL((qkv_append_rows_dev_kv8_kernel<E, D>), grid, dim3(256), 0, ft_stream(),
                          mptr<typename E::T>(qkv), cptr<float>(cos_t), cptr<float>(sin_t), cptr<int>(pos0),
@@ -562,7 +449,7 @@ void kv_quantize_prefill(const at::Tensor& k, const at::Tensor& v, const at::Ten
   const at::DeviceGuard guard(k.device());
   const long nvec = (long)(k.numel() / 8);
   TORCH_CHECK((nvec + 255) / 256 <= INT_MAX, op, ": too many workgroups");
-  FT_DISPATCH_E16(k.scalar_type(), FT_KV8_D(s.d, {
+  FT_DISPATCH_E16(k.scalar_type(), FT_DECODE_D(s.d, {
     hipLaunchKernelGGL((kv_quantize_prefill_kernel<E, D>), dim3((unsigned)((nvec + 255) / 256), 2), dim3(256), 0,
                        ft_stream(), cptr<typename E::T>(k), cptr<typename E::T>(v), mptr<uint8_t>(kc),
                        mptr<uint8_t>(vc), mptr<float>(ks), mptr<float>(vs), nvec, (int)s.hkv, (long)s.smax, (long)k.stride(0),
@@ -583,9 +470,9 @@ at::Tensor attn_kv8(const at::Tensor& q, const at::Tensor& kc, const at::Tensor&
   auto part = at::empty({nchunks, hq, s.d + 2}, q.options().dtype(at::kFloat));
   auto o = at::empty({hq * s.d}, q.options());
   const int G = (int)(hq / s.hkv);
-  FT_DISPATCH_E16(q.scalar_type(), FT_KV8_D(s.d, {
+  FT_DISPATCH_E16(q.scalar_type(), FT_DECODE_D(s.d, {
     const float scale = 1.f / sqrtf((float)D);
-    FT_KV8_GT(G, hipLaunchKernelGGL((decode_attn_kv8_kernel<E, D, GT>), dim3((unsigned)s.hkv, nchunks), dim3(256), 0,
+    FT_DECODE_GT(G, hipLaunchKernelGGL((decode_attn_kv8_kernel<E, D, GT>), dim3((unsigned)s.hkv, nchunks), dim3(256), 0,
                                     ft_stream(), cptr<typename E::T>(q), cptr<uint8_t>(kc), cptr<uint8_t>(vc),
                                     cptr<float>(ks), cptr<float>(vs), mptr<float>(part), (int)hq, (int)s.hkv,
                                     (long)s.smax, (int)n_keys, scale));
@@ -605,10 +492,10 @@ void attn_rows_kv8_into(const char* op, const at::Tensor& q, const at::Tensor& k
                         const at::Tensor& o) {
   const int B = (int)q.size(0), G = (int)(hq / s.hkv);
   const dim3 grid((unsigned)s.hkv, max_chunks, B);
-  FT_DISPATCH_E16(q.scalar_type(), FT_KV8_D(s.d, {
+  FT_DISPATCH_E16(q.scalar_type(), FT_DECODE_D(s.d, {
     const float scale = 1.f / sqrtf((float)D);
     if (ctl != nullptr) {
-      FT_KV8_GT(G, hipLaunchKernelGGL((decode_attn_rows_dev_kv8_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),
+      FT_DECODE_GT(G, hipLaunchKernelGGL((decode_attn_rows_dev_kv8_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),
                                       cptr<typename E::T>(q), cptr<uint8_t>(kc), cptr<uint8_t>(vc), cptr<float>(ks),
                                       cptr<float>(vs), mptr<float>(part), cptr<int>(pos0), cptr<int>(*ctl),
                                       (long)q.stride(0), (int)hq, (int)s.hkv, (long)s.smax, scale));
@@ -617,7 +504,7 @@ void attn_rows_kv8_into(const char* op, const at::Tensor& q, const at::Tensor& k
                          cptr<float>(part), mptr<typename E::T>(o), cptr<int>(pos0), cptr<int>(*ctl), (int)s.smax,
                          max_chunks, (int)hq);
     } else {
-      FT_KV8_GT(G, hipLaunchKernelGGL((decode_attn_rows_kv8_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),
+      FT_DECODE_GT(G, hipLaunchKernelGGL((decode_attn_rows_kv8_kernel<E, D, GT>), grid, dim3(256), 0, ft_stream(),
                                       cptr<typename E::T>(q), cptr<uint8_t>(kc), cptr<uint8_t>(vc), cptr<float>(ks),
                                       cptr<float>(vs), mptr<float>(part), cptr<int>(pos0), t, max_keys,
                                       (long)q.stride(0), (int)hq, (int)s.hkv, (long)s.smax, scale));
@@ -654,15 +541,10 @@ void attn_rows_dev_kv8(const at::Tensor& q, const at::Tensor& kc, const at::Tens
   const KvShape s = check_kv8(op, q, kc, vc, ks, vs, true);
   check_pos0(op, pos0, q);
   check_ctl(op, ctl, q);
-  const int64_t B = q.size(0), hq = q_heads(op, q.size(1), s);
+  const int64_t hq = q_heads(op, q.size(1), s);
   const int64_t max_chunks = (s.smax + DECODE_CHUNK - 1) / DECODE_CHUNK;
   TORCH_CHECK(max_chunks <= 65535, op, ": too many key chunks");
-  TORCH_CHECK(part.is_cuda() && part.device() == q.device() && part.scalar_type() == at::kFloat &&
-                  part.is_contiguous() && part.numel() == B * max_chunks * hq * (s.d + 2),
-              op, ": part must be a contiguous fp32 [B, ceil(Smax / ", DECODE_CHUNK, "), Hq, D + 2] tensor");
-  TORCH_CHECK(o.is_cuda() && o.device() == q.device() && o.scalar_type() == q.scalar_type() && o.is_contiguous() &&
-                  o.dim() == 2 && o.size(0) == B && o.size(1) == hq * s.d,
-              op, ": o must be a contiguous [B, Hq D] tensor of q's dtype");
+  check_attn_out(op, q, part, o, max_chunks, hq, s.d);
   const at::DeviceGuard guard(q.device());
   attn_rows_kv8_into(op, q, kc, vc, ks, vs, pos0, &ctl, 0, (int)s.smax, (int)max_chunks, s, hq, part, o);
 }

@@ -50,10 +50,8 @@
 // The contract is batch invariance, not the bits of gemv_rows (the order of the sum differs): y[r] depends
 // on x[r] and the weight alone -- not on R, on the other rows, or on the row's place in the batch; R = 1
 // runs the same kernel with 15 idle columns. Every op returns the same bits from run to run.
-#include <climits>
-
+#include "decode_host.h"  // check_vec, check_residual
 #include "fp8.h"
-#include "torch_utils.h"
 
 namespace {
 
@@ -284,19 +282,13 @@ int mma_split(int64_t rows, int64_t K) {
   return (int)std::max<int64_t>(1, std::min(want, cap));
 }
 
-void mma_check_vec(const char* op, const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
-}
-
 // x [R, K], w [rows, K] (weights in x's dtype, or uint8 codes with scale [rows]); the result is [R, N].
 template <bool SWIGLU, bool W8>
 at::Tensor gemm_mma_impl(const char* op, const at::Tensor& x, const at::Tensor& w,
                          const c10::optional<at::Tensor>& scale, const c10::optional<at::Tensor>& residual,
                          int64_t split) {
-  mma_check_vec(op, x, "x");
-  mma_check_vec(op, w, W8 ? "codes" : "w");
+  check_vec(op, x, "x");
+  check_vec(op, w, W8 ? "codes" : "w");
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf, op, ": x must be bf16 or fp16");
   TORCH_CHECK(w.scalar_type() == (W8 ? at::kByte : x.scalar_type()), op,
               W8 ? ": codes must be uint8 (e4m3 bit patterns)" : ": w must have x's dtype");
@@ -317,10 +309,8 @@ at::Tensor gemm_mma_impl(const char* op, const at::Tensor& x, const at::Tensor& 
   const int64_t N = SWIGLU ? rows / 2 : rows;
   const bool has_res = residual.has_value() && residual->defined();
   if (has_res) {
-    mma_check_vec(op, *residual, "residual");
-    TORCH_CHECK(!SWIGLU && residual->scalar_type() == x.scalar_type() && residual->device() == x.device() &&
-                    residual->dim() == 2 && residual->size(0) == R && residual->size(1) == N,
-                op, ": residual must be [R, N] in x's dtype, on its device");
+    check_vec(op, *residual, "residual");
+    check_residual(op, *residual, x, N);
   }
   const int64_t nch = (K + MM_KC - 1) / MM_KC;
   TORCH_CHECK(split >= 0 && split <= std::min<int64_t>(nch, MM_MAX_SPLIT), op, ": split must be 0 (chosen from the "

@@ -50,9 +50,7 @@
 //
 // Plain vector code: no matrix cores, no atomics, no inline assembly. Every reduction has a fixed
 // order, so each op returns the same bits from run to run.
-#include <climits>
-
-#include "torch_utils.h"
+#include "decode_host.h"  // check_vec, check_residual, the rows tile
 
 namespace {
 
@@ -292,12 +290,6 @@ __global__ __launch_bounds__(256) void quantize_mxfp4_kernel(const typename E::T
   scales[g] = (uint8_t)e;
 }
 
-void check_vec(const char* op, const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
-}
-
 // codes uint8 [rows, K / 2] and scales uint8 [rows, K / 32] of one weight, on `dev`
 void check_pair(const char* op, const at::Tensor& codes, const at::Tensor& scales, c10::Device dev) {
   check_vec(op, codes, "codes");
@@ -359,30 +351,19 @@ at::Tensor gemv_mx4_impl(const char* op, bool rows, const at::Tensor& x, const a
   TORCH_CHECK(!SWIGLU || nrows % 2 == 0, op, ": codes13 must be [2H, K / 2]");
   const int64_t N = SWIGLU ? nrows / 2 : nrows;
   const bool has_res = residual.has_value() && residual->defined();
-  if (has_res) {
-    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() && residual->scalar_type() == x.scalar_type() &&
-                    residual->device() == x.device() && residual->dim() == x.dim() && residual->numel() == R * N &&
-                    residual->size(-1) == N,
-                op, ": residual must be a contiguous tensor of the result's shape, in x's dtype, on its device");
-  }
-  const int rt = R == 1 ? 1 : R == 2 ? 2 : R <= 4 ? 4 : MX_ROWS_TILE;
+  if (has_res) check_residual(op, *residual, x, N);
+  const int rt = rows_tile(R, MX_ROWS_TILE);
   const int64_t ntiles = (R + rt - 1) / rt;
   const int64_t blocks = (N + MX_WG_ROWS - 1) / MX_WG_ROWS * ntiles;
   TORCH_CHECK(blocks <= INT_MAX, op, ": too many workgroups (output rows x row tiles)");
   const at::DeviceGuard guard(x.device());
   auto y = rows ? at::empty({R, N}, x.options()) : at::empty({N}, x.options());
-#define FT_GEMV_MX4(RT)                                                                                          \
-  hipLaunchKernelGGL((gemv_mx4_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(MX_THREADS), 0, ft_stream(), \
-                     cptr<typename E::T>(x), cptr<uint8_t>(codes), cptr<uint8_t>(scales),                        \
-                     has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y), (int)N, (int)K,  \
-                     (int)R, (int)ntiles)
-  FT_DISPATCH_E16(x.scalar_type(), {
-    if (rt == 1) FT_GEMV_MX4(1);
-    else if (rt == 2) FT_GEMV_MX4(2);
-    else if (rt == 4) FT_GEMV_MX4(4);
-    else FT_GEMV_MX4(MX_ROWS_TILE);
-  });
-#undef FT_GEMV_MX4
+  FT_DISPATCH_E16(x.scalar_type(), FT_ROWS_TILE(rt, MX_ROWS_TILE, {
+    hipLaunchKernelGGL((gemv_mx4_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(MX_THREADS), 0, ft_stream(),
+                       cptr<typename E::T>(x), cptr<uint8_t>(codes), cptr<uint8_t>(scales),
+                       has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y), (int)N, (int)K,
+                       (int)R, (int)ntiles);
+  }));
   FT_LAUNCH_CHECK();
   return y;
 }

@@ -27,10 +27,8 @@
 // Plain vector code: no matrix cores, no atomics, and no inline assembly but for the empty register
 // barrier (no instruction in it) in scaled() of fp8.h, which says why it is there. Every reduction has a fixed
 // order, so each op returns the same bits from run to run.
-#include <climits>
-
+#include "decode_host.h"  // check_vec, check_residual, the rows tile
 #include "fp8.h"
-#include "torch_utils.h"
 
 namespace {
 
@@ -211,24 +209,16 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const typename E::T*
     __syncthreads();
     m = max(max(red[0], red[1]), max(red[2], red[3]));
   }
-  const bool finite = m < 0x7f800000u;
-  const float amax = __uint_as_float(m);
-  // amax == 0: scale 1, codes are the signed zeros of the weights. A non-finite row: NaN scale, zero
-  // codes. inv is capped at the largest float: below amax = 448 / FLT_MAX the quotient overflows.
-  float inv = 0.f, sc = __uint_as_float(0x7fc00000u);
-  if (finite) {
-    inv = m == 0u ? 1.f : fminf(__fdiv_rn(448.f, amax), 3.402823466e+38f);
-    sc = m == 0u ? 1.f : __fdiv_rn(amax, 448.f);
-  }
-  if (li == 0) scale[row] = sc;
+  const E4m3Row q = e4m3_row(m);
+  if (li == 0) scale[row] = q.scale;
   uint8_t* cr = codes + (long)row * K;
   for (int k = li * W8_VEC; k < K; k += LANES * W8_VEC) {
     float f[W8_VEC];
     uint4 c = make_uint4(0u, 0u, 0u, 0u);
-    if (finite) {
+    if (q.finite) {
       ld16<E>(wr + k, f);
 #pragma unroll
-      for (int j = 0; j < W8_VEC; ++j) f[j] = __fmul_rn(f[j], inv);
+      for (int j = 0; j < W8_VEC; ++j) f[j] = __fmul_rn(f[j], q.inv);
       c = make_uint4(f32x4_to_fp8(f), f32x4_to_fp8(f + 4), f32x4_to_fp8(f + 8), f32x4_to_fp8(f + 12));
     }
     *reinterpret_cast<uint4*>(cr + k) = c;
@@ -236,12 +226,6 @@ __global__ __launch_bounds__(256) void quantize_rows_kernel(const typename E::T*
 }
 
 constexpr int QUANT_WAVE_MAX_K = 2048;
-
-void check_vec(const char* op, const at::Tensor& t, const char* name) {
-  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU tensor");
-  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name, " must be 16-byte aligned");
-}
 
 void quantize_rows_e4m3_out(const at::Tensor& w, at::Tensor codes, at::Tensor scale) {
   const char* op = "quantize_rows_e4m3";
@@ -308,32 +292,21 @@ at::Tensor gemv_w8_impl(const char* op, bool rows, const at::Tensor& x, const at
               op, ": scale must be a contiguous fp32 tensor with one entry per code row, on the codes' device");
   const int64_t N = SWIGLU ? nrows / 2 : nrows;
   const bool has_res = residual.has_value() && residual->defined();
-  if (has_res) {
-    TORCH_CHECK(residual->is_cuda() && residual->is_contiguous() && residual->scalar_type() == x.scalar_type() &&
-                    residual->device() == x.device() && residual->dim() == x.dim() && residual->numel() == R * N &&
-                    residual->size(-1) == N,
-                op, ": residual must be a contiguous tensor of the result's shape, in x's dtype, on its device");
-  }
+  if (has_res) check_residual(op, *residual, x, N);
   constexpr int TOP = SWIGLU ? W8_SWIGLU_ROWS_TILE : W8_ROWS_TILE;
-  const int rt = R == 1 ? 1 : R == 2 ? 2 : (R <= 4 || TOP == 4) ? 4 : 8;
+  const int rt = rows_tile(R, TOP);
   const int waves = rt == 1 ? 4 : 8;
   const int64_t ntiles = (R + rt - 1) / rt;
   const int64_t blocks = (N + waves - 1) / waves * ntiles;
   TORCH_CHECK(blocks <= INT_MAX, op, ": too many workgroups (output rows x row tiles)");
   const at::DeviceGuard guard(x.device());
   auto y = rows ? at::empty({R, N}, x.options()) : at::empty({N}, x.options());
-#define FT_GEMV_W8(RT)                                                                                          \
-  hipLaunchKernelGGL((gemv_w8_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(W8Tile<RT>::THREADS), 0,     \
-                     ft_stream(), cptr<typename E::T>(x), cptr<uint8_t>(codes), cptr<float>(scale),             \
-                     has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y), (int)N, (int)K, \
-                     (int)R, (int)ntiles)
-  FT_DISPATCH_E16(x.scalar_type(), {
-    if (rt == 1) FT_GEMV_W8(1);
-    else if (rt == 2) FT_GEMV_W8(2);
-    else if (rt == 4) FT_GEMV_W8(4);
-    else FT_GEMV_W8(TOP);
-  });
-#undef FT_GEMV_W8
+  FT_DISPATCH_E16(x.scalar_type(), FT_ROWS_TILE(rt, TOP, {
+    hipLaunchKernelGGL((gemv_w8_kernel<E, SWIGLU, RT>), dim3((unsigned)blocks), dim3(W8Tile<RT>::THREADS), 0,
+                       ft_stream(), cptr<typename E::T>(x), cptr<uint8_t>(codes), cptr<float>(scale),
+                       has_res ? cptr<typename E::T>(*residual) : nullptr, mptr<typename E::T>(y), (int)N, (int)K,
+                       (int)R, (int)ntiles);
+  }));
   FT_LAUNCH_CHECK();
   return y;
 }

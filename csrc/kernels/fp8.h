@@ -47,6 +47,27 @@ __device__ __forceinline__ uint32_t f32x4_to_fp8(const float* f) {
   return f32x2_to_fp8(f[0], f[1]) | (f32x2_to_fp8(f[2], f[3]) << 16);
 }
 
+// The row rule of utils/fp8.py from m, the bit pattern of the row's amax = max |x| (as an integer: for
+// non-negative floats the integer order is the float order, infinity and every NaN above all finite
+// values): code = e4m3_rne(x * inv), value = code * scale. amax == 0: scale 1, the codes are the signed
+// zeros of the row. A non-finite row: NaN scale, and the caller stores zero codes. inv is capped at the
+// largest float: below amax = 448 / FLT_MAX the quotient overflows. The weight quantizer and the KV
+// cache both quantize by this, so the two formats cannot drift apart.
+struct E4m3Row {
+  bool finite;
+  float inv, scale;
+};
+
+__device__ __forceinline__ E4m3Row e4m3_row(uint32_t m) {
+  E4m3Row r{m < 0x7f800000u, 0.f, __uint_as_float(0x7fc00000u)};
+  const float amax = __uint_as_float(m);
+  if (r.finite) {
+    r.inv = m == 0u ? 1.f : fminf(__fdiv_rn(448.f, amax), 3.402823466e+38f);
+    r.scale = m == 0u ? 1.f : __fdiv_rn(amax, 448.f);
+  }
+  return r;
+}
+
 // s * scale (+ residual): separately rounded fp32 operations. Each result passes an opaque register
 // barrier (the empty asm of common.h's pin8), so the compiler can neither contract the two into one
 // fma nor merge the last of them with the caller's conversion to fp16 into a mixed-precision fma

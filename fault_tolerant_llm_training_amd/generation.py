@@ -68,6 +68,10 @@ logits on the unquantized K / V and stores their codes (``D.kv_quantize_prefill_
 model-dtype cache would have held it, so a row appended by a decode step and a row written by the prefill
 follow one rule. It composes with ``weights``, ``mma`` and ``graph``; with ``kv_dtype="model"`` every path
 returns the bits it returned before. An fp32 or fp64 model on the GPU is refused.
+
+Which ops a pass runs is decided in two places: :func:`_products` maps ``(weights, mma)`` to the product
+ops (the weight classes name theirs), and ``_KV_OPS`` maps ``kv_dtype`` to the six ops that touch the
+cache. The decode loops take what those give and do not branch on either.
 """
 from __future__ import annotations
 
@@ -225,6 +229,10 @@ class Fp8Weights:
 
     K_MULTIPLE, K_WHY = 16, "16-byte vectors of e4m3 codes"
     _quantize = staticmethod(D.quantize_rows)
+    # the products on a (codes, scale) pair, plain and SwiGLU: one row, rows, rows on the matrix cores
+    _MV = (D.gemv_w8, D.gemv_swiglu_w8)
+    _MV_ROWS = (D.gemv_rows_w8, D.gemv_swiglu_rows_w8)
+    _MV_MMA = (D.gemm_rows_mma_w8, D.gemm_swiglu_rows_mma_w8)
 
     def __init__(self, model):
         flat, who = model.flat, type(self).__name__
@@ -277,46 +285,59 @@ class Mxfp4Weights(Fp8Weights):
 
     K_MULTIPLE, K_WHY = 32, "one MXFP4 scale per block of 32 elements"
     _quantize = staticmethod(D.quantize_rows_mx4)
+    _MV = (D.gemv_mx4, D.gemv_swiglu_mx4)
+    _MV_ROWS = (D.gemv_rows_mx4, D.gemv_swiglu_rows_mx4)
+    _MV_MMA = None  # no matrix-core kernels: what _check_mma refuses
 
 
-# One product of a pass: the model's weight, or its quantized pair ``q`` (``(codes, scale)`` of an
-# :class:`Fp8Weights`, ``(codes, scales)`` of an :class:`Mxfp4Weights`: ``mx4`` says which) where given.
-def _mv(x, w, q, mx4=False):
-    if q is None:
-        return D.gemv(x, w)
-    return D.gemv_mx4(x, q[0], q[1]) if mx4 else D.gemv_w8(x, q[0], q[1])
+class _OwnWeights:
+    """The product ops on the model's own weights, under the names the quantized classes give theirs."""
+
+    _MV = (D.gemv, D.gemv_swiglu)
+    _MV_ROWS = (D.gemv_rows, D.gemv_swiglu_rows)
+    _MV_MMA = (D.gemm_rows_mma, D.gemm_swiglu_rows_mma)
 
 
-def _mv_swiglu(x, w13, q, mx4=False):
-    if q is None:
-        return D.gemv_swiglu(x, w13)
-    return D.gemv_swiglu_mx4(x, q[0], q[1]) if mx4 else D.gemv_swiglu_w8(x, q[0], q[1])
+def _products(weights: Optional[Fp8Weights], mma: bool = False):
+    """``(mv, mv_swiglu, mv_rows, mv_swiglu_rows)`` of a pass. Each is called on an activation and a
+    weight's operands (:func:`_layer_operands`, :func:`_head_operands`); ``mma``, which :func:`_check_mma`
+    has let through, puts the rows forms on the matrix cores."""
+    ops = _OwnWeights if weights is None else weights
+    return ops._MV + (ops._MV_MMA if mma else ops._MV_ROWS)
 
 
-def _mv_rows(x, w, q, mma=False, mx4=False):
-    if mx4 and q is not None:  # _check_mma has refused mma
-        return D.gemv_rows_mx4(x, q[0], q[1])
-    if mma:
-        return D.gemm_rows_mma(x, w) if q is None else D.gemm_rows_mma_w8(x, q[0], q[1])
-    return D.gemv_rows(x, w) if q is None else D.gemv_rows_w8(x, q[0], q[1])
+def _layer_operands(layer, weights: Optional[Fp8Weights], i: int):
+    """What the products take after the activation for ``wqkv``, ``wo``, ``[w1; w3]`` and ``w2`` of layer
+    ``i``: the model's weight, or its quantized pair of ``weights``."""
+    if weights is not None:
+        return weights.layers[i]
+    at, ff = layer.attention, layer.feed_forward
+    return (at.wqkv,), (at.wo.weight,), (ff.w13,), (ff.w2.weight,)
 
 
-def _mv_swiglu_rows(x, w13, q, mma=False, mx4=False):
-    if mx4 and q is not None:
-        return D.gemv_swiglu_rows_mx4(x, q[0], q[1])
-    if mma:
-        return D.gemm_swiglu_rows_mma(x, w13) if q is None else D.gemm_swiglu_rows_mma_w8(x, q[0], q[1])
-    return D.gemv_swiglu_rows(x, w13) if q is None else D.gemv_swiglu_rows_w8(x, q[0], q[1])
+def _head_operands(model, weights: Optional[Fp8Weights]):
+    return (model.output.weight,) if weights is None else weights.head
 
 
-def _kv8(cache, i: int):
-    """Layer i of an FP8 cache as the four operands of the ``_kv8`` ops."""
-    return cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i]
+# The six ops of a pass that touch the cache, by ``kv_dtype``: append and attend, their ``_rows`` forms and
+# their ``_rows_dev`` forms. The two families take the same arguments around the cache operands (_kv).
+_KV_OPS = {
+    "model": (D.qkv_append_, D.attn, D.qkv_append_rows_, D.attn_rows, D.qkv_append_rows_dev_, D.attn_rows_dev),
+    "fp8": (D.qkv_append_kv8_, D.attn_kv8, D.qkv_append_rows_kv8_, D.attn_rows_kv8, D.qkv_append_rows_dev_kv8_,
+            D.attn_rows_dev_kv8),
+}
+
+
+def _kv(cache, i: int):
+    """Layer i's cache operands of those ops: ``k`` and ``v``, and for an FP8 cache their two scales."""
+    if cache.kv_dtype == "fp8":
+        return cache.k[i], cache.v[i], cache.k_scale[i], cache.v_scale[i]
+    return cache.k[i], cache.v[i]
 
 
 def _check_mma(model, mma: bool, weights: Optional[Fp8Weights] = None) -> None:
     flat = model.flat
-    if mma and isinstance(weights, Mxfp4Weights):
+    if mma and weights is not None and weights._MV_MMA is None:
         raise ValueError("mma=True has no MXFP4 kernels: decode Mxfp4Weights with mma=False")
     if mma and flat.device.type == "cuda" and flat.dtype not in (torch.bfloat16, torch.float16):
         raise ValueError(f"mma=True needs a bf16 or fp16 model on the GPU, got {flat.dtype}")
@@ -337,8 +358,7 @@ def _final_logits(model, h: torch.Tensor, d: Optional[torch.Tensor],
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return _mv(hn.reshape(-1), model.output.weight, None if weights is None else weights.head,
-               isinstance(weights, Mxfp4Weights))
+    return _products(weights)[0](hn.reshape(-1), *_head_operands(model, weights))
 
 
 @torch.no_grad()
@@ -401,26 +421,23 @@ def decode_step(model, token: Union[int, torch.Tensor], cache: KVCache,
     model._wait(emb_r)
     h = Fx.embedding(tok, model.tok_embeddings.weight, None).view(1, -1)
     cos, sin = model.rope_cos, model.rope_sin
-    mx4 = isinstance(weights, Mxfp4Weights)
+    mv, mv_swiglu = _products(weights)[:2]
+    append, attend = _KV_OPS[cache.kv_dtype][:2]
     d = None
     for i, layer in enumerate(model.layers.values()):
         model._wait(layer_r[i])
-        at, ff = layer.attention, layer.feed_forward
-        qqkv, qo, q13, q2 = (None,) * 4 if weights is None else weights.layers[i]
+        wqkv, wo, w13, w2 = _layer_operands(layer, weights, i)
+        kv = _kv(cache, i)
         if d is None:
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = _mv(xn.reshape(-1), at.wqkv, qqkv, mx4)
-        if cache.kv_dtype == "fp8":
-            D.qkv_append_kv8_(qkv, cos, sin, pos, *_kv8(cache, i))
-            o = D.attn_kv8(qkv[: hq * hd], *_kv8(cache, i), pos + 1)
-        else:
-            D.qkv_append_(qkv, cos, sin, pos, cache.k[i], cache.v[i])
-            o = D.attn(qkv[: hq * hd], cache.k[i], cache.v[i], pos + 1)
-        da = _mv(o, at.wo.weight, qo, mx4)
+        qkv = mv(xn.reshape(-1), *wqkv)
+        append(qkv, cos, sin, pos, *kv)
+        o = attend(qkv[: hq * hd], *kv, pos + 1)
+        da = mv(o, *wo)
         h, hn = Fx.add_norm(h, da.view(1, -1), layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = _mv(_mv_swiglu(hn.reshape(-1), ff.w13, q13, mx4), ff.w2.weight, q2, mx4).view(1, -1)
+        d = mv(mv_swiglu(hn.reshape(-1), *w13), *w2).view(1, -1)
     cache.length = pos + 1
     return _final_logits(model, h, d, weights)
 
@@ -438,7 +455,7 @@ def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional
     ln = a.norm_type == "layernorm"
     hq, hd = a.n_heads, a.head_dim
     emb_r, layer_r, final_r = model._ranges
-    mx4 = isinstance(weights, Mxfp4Weights)
+    mv_rows, mv_swiglu_rows = _products(weights, mma)[2:]
     if wait is not None:
         wait(emb_r)
     h = Fx.embedding(tok, model.tok_embeddings.weight, None).view(tok.shape[0], -1)
@@ -446,25 +463,24 @@ def _rows_pass(model, tok: torch.Tensor, append, attend, wait, weights: Optional
     for i, layer in enumerate(model.layers.values()):
         if wait is not None:
             wait(layer_r[i])
-        at, ff = layer.attention, layer.feed_forward
-        qqkv, qo, q13, q2 = (None,) * 4 if weights is None else weights.layers[i]
+        wqkv, wo, w13, w2 = _layer_operands(layer, weights, i)
         if d is None:
             xn = Fx.norm(h, layer.attention_norm.weight, None, a.norm_eps, ln)
         else:
             h, xn = Fx.add_norm(h, d, layer.attention_norm.weight, None, a.norm_eps, ln)
-        qkv = _mv_rows(xn, at.wqkv, qqkv, mma, mx4)
+        qkv = mv_rows(xn, *wqkv)
         append(i, qkv)
         o = attend(i, qkv[:, : hq * hd])
-        da = _mv_rows(o, at.wo.weight, qo, mma, mx4)
+        da = mv_rows(o, *wo)
         h, hn = Fx.add_norm(h, da, layer.ffn_norm.weight, None, a.norm_eps, ln)
-        d = _mv_rows(_mv_swiglu_rows(hn, ff.w13, q13, mma, mx4), ff.w2.weight, q2, mma, mx4)
+        d = mv_rows(mv_swiglu_rows(hn, *w13), *w2)
     if wait is not None:
         wait(final_r)
     if d is None:
         hn = Fx.norm(h, model.norm.weight, None, a.norm_eps, ln)
     else:
         _, hn = Fx.add_norm(h, d, model.norm.weight, None, a.norm_eps, ln)
-    return _mv_rows(hn, model.output.weight, None if weights is None else weights.head, mma, mx4)
+    return mv_rows(hn, *_head_operands(model, weights))
 
 
 @torch.no_grad()
@@ -486,16 +502,11 @@ def decode_step_rows(model, tokens: Union[Sequence[int], torch.Tensor], cache: B
     tok = torch.as_tensor(tokens, dtype=torch.int64).reshape(B, 1).to(dev)
     cos, sin = model.rope_cos, model.rope_sin
     pos0, lengths = cache.pos0, cache.lengths
-    if cache.kv_dtype == "fp8":
-        logits = _rows_pass(
-            model, tok,
-            lambda i, qkv: D.qkv_append_rows_kv8_(qkv, cos, sin, pos0, t, *_kv8(cache, i), lengths),
-            lambda i, q: D.attn_rows_kv8(q, *_kv8(cache, i), pos0, t, lengths), model._wait, weights, mma)
-    else:
-        logits = _rows_pass(
-            model, tok,
-            lambda i, qkv: D.qkv_append_rows_(qkv, cos, sin, pos0, t, cache.k[i], cache.v[i], lengths),
-            lambda i, q: D.attn_rows(q, cache.k[i], cache.v[i], pos0, t, lengths), model._wait, weights, mma)
+    append, attend = _KV_OPS[cache.kv_dtype][2:4]
+    logits = _rows_pass(
+        model, tok,
+        lambda i, qkv: append(qkv, cos, sin, pos0, t, *_kv(cache, i), lengths),
+        lambda i, q: attend(q, *_kv(cache, i), pos0, t, lengths), model._wait, weights, mma)
     cache.steps = t + 1
     return logits
 
@@ -585,18 +596,11 @@ class DecodeGraph:
         model, cache, ctl, pos0 = self.model, self.cache, self.ctl, self.pos0
         cos, sin = model.rope_cos, model.rope_sin
         D.sample_dev_(self.logits, ctl, self.tok, self.out)
-        if cache.kv_dtype == "fp8":
-            logits = _rows_pass(
-                model, self.tok,
-                lambda i, qkv: D.qkv_append_rows_dev_kv8_(qkv, cos, sin, pos0, ctl, *_kv8(cache, i)),
-                lambda i, q: D.attn_rows_dev_kv8(q, *_kv8(cache, i), pos0, ctl, self.part, self.o), None,
-                self.weights, self.mma)
-        else:
-            logits = _rows_pass(
-                model, self.tok,
-                lambda i, qkv: D.qkv_append_rows_dev_(qkv, cos, sin, pos0, ctl, cache.k[i], cache.v[i]),
-                lambda i, q: D.attn_rows_dev(q, cache.k[i], cache.v[i], pos0, ctl, self.part, self.o), None,
-                self.weights, self.mma)
+        append, attend = _KV_OPS[cache.kv_dtype][4:]
+        logits = _rows_pass(
+            model, self.tok,
+            lambda i, qkv: append(qkv, cos, sin, pos0, ctl, *_kv(cache, i)),
+            lambda i, q: attend(q, *_kv(cache, i), pos0, ctl, self.part, self.o), None, self.weights, self.mma)
         self.logits.copy_(logits)
         D.ctl_advance_(ctl)
 
@@ -762,14 +766,7 @@ def generate(model, prompt_ids: Sequence[int], max_new_tokens: int, temperature:
     prompt = [int(t) for t in prompt_ids]
     n_new = int(max_new_tokens)
     a = model.model_args
-    if not prompt:
-        raise ValueError("generate needs a prompt of at least one token")
-    if n_new < 0 or len(prompt) + n_new > a.seq_len:
-        raise ValueError(f"prompt ({len(prompt)}) + new tokens ({n_new}) exceed the model's sequence length "
-                         f"{a.seq_len}")
-    bad = [t for t in prompt if not 0 <= t < a.vocab_size]
-    if bad:
-        raise ValueError(f"prompt id {bad[0]} outside the vocabulary [0, {a.vocab_size})")
+    _check_request(a, prompt, n_new, "generate")
     if n_new == 0:
         return []
     flat = model.flat
